@@ -24,7 +24,15 @@ exchange is `exchange_bytes` (K = 20, 48 windows, 8 ranks: 133 GB beside the
 engine); the line reports the measured peak (`peak_hbm_gb`).  `n_gpus` is the world size the process group
 reports.  Rank 0 prints ONE JSON line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|4]
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps
+and the result line.  `--full` adds every other measurement after the timed loop
+(the per-kernel / roofline probe of one step, the single-window latency, restore_video,
+Whisper features, the CPU oracle baseline).  `--dump-outputs DIR` writes what the last
+timed step computed (rank 0's fp32 pasted frames and their uint8 clip, a fixed seeded
+sample when larger than DUMP_MAX_ELEMS) as DIR/<name>.npy, float32; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|4] [--full] [--dump-outputs DIR]
 """
 import argparse
 import datetime
@@ -417,6 +425,22 @@ def exchange_bytes(world, K, nw, F=16, R=256):
             + 2 * U8_CHUNK * 3 * R * R * 4)
 
 
+DUMP_MAX_ELEMS = 4 * 1024 * 1024  # per array: 16 MB as float32, two arrays per dump
+
+
+def dump_outputs(path, arrays):
+    """Write each tensor as path/<name>.npy in float32: whole when it has at most
+    DUMP_MAX_ELEMS elements, else the elements at a fixed seeded set of flat indices
+    (sorted; the same for every run of the same shape)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(20))
+            t = t.reshape(-1)[idx.sort().values.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -562,6 +586,10 @@ def worker(args):
                    "global_batch": world * nw * F, "resolution": R,
                    "parallelism": f"dp{world} (window sharding, RCCL all-gather of decoded frames)"},
     }
+    if args.dump_outputs and rank == 0:
+        # rank 0's last timed step: its windows [(K-1)*nw, K*nw), which lead the clip order
+        last = slice((K - 1) * nw, K * nw)
+        dump_outputs(args.dump_outputs, {"frames": mine[last], "frames_u8": gathered[last]})
     gib = 1024 ** 3
     res["memory"] = {"exchange_gb": round(exchange_bytes(world, K, nw, F, R) / gib, 3),
                      "exchange_gb_at_8_ranks_k20": round(exchange_bytes(8, 20, nw, F, R) / gib, 3)}
@@ -587,6 +615,18 @@ def worker(args):
         torch.cuda.get_device_properties(device).total_memory / gib, 1)})
     res["memory"]["footprint_gb_at_8_ranks_k20"] = round(res["memory"]["engine_gb"] +
                                                          res["memory"]["exchange_gb_at_8_ranks_k20"], 3)
+    Bu = 2 if args.guidance > 1 else 1
+    unet_tf, enc_tf, dec_tf = WORK_TF[R]
+    tf_per_frame = (args.inference_steps * unet_tf * Bu + 32 * enc_tf + 16 * dec_tf) / 16
+    res.update({"batch_ms_gpu_events": round(window_ms, 3),
+                "window_mfma_frac": round(tf_per_frame * value / world / PEAK_BF16_TF, 4)})
+    if not args.full:
+        # a plain run ends here; everything below takes runs of its own
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     probe, attn_probe, blk_probe = step_probe(eng, device)
     single = None
     if rank == 0 and nw > 1 and not args.no_single_window:
@@ -605,13 +645,8 @@ def worker(args):
     restore = None
     if rank == 0 and R == 256:
         restore = restore_probe(eng.out[:F].clone(), device)
-    Bu = 2 if args.guidance > 1 else 1
-    unet_tf, enc_tf, dec_tf = WORK_TF[R]
-    tf_per_frame = (args.inference_steps * unet_tf * Bu + 32 * enc_tf + 16 * dec_tf) / 16
     res.update({
-        "batch_ms_gpu_events": round(window_ms, 3),
         "single_window": single,
-        "window_mfma_frac": round(tf_per_frame * value / world / PEAK_BF16_TF, 4),
         "roofline": {"bound": "mfma",
                      "kernel": "conv_gemm family: every ls_conv2d call of one UNet fwd (conv_gemm_* tiled / "
                                "gemm_rowblock / conv3x3_halo GEMM + split-K reduce; one launch per call)",
@@ -670,6 +705,11 @@ def parse_args():
     ap.add_argument("--attn-precision", choices=("bf16", "fp8"), default=None,
                     help="spatial self attention: bf16 (default) or fp8 P.V (configs[4]'s fp8 option)")
     ap.add_argument("--inference-steps", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the step probe (roofline, attention), the single-window "
+                         "latency, restore_video, Whisper and the CPU baseline (the --no-* switches drop legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, seeded sample if large)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-whisper", action="store_true")
     ap.add_argument("--no-graphs", action="store_true")

@@ -3,7 +3,7 @@ repo's kernels on the UNet's contraction shapes (VERDICT r1 'What's weak' 3).
 
   * plain square GEMMs (4096^3, 8192^3) through torch.matmul (hipBLASLt) and through
     ls_conv2d (ksize 1: the repo's DMA GEMM) -- the best of them is the ceiling
-    bench.py reports as roofline.peak_measured;
+    bench.py --full reports as roofline.peak_measured;
   * every distinct UNet conv / linear shape of one step at 16 windows per call:
     ls_conv2d (with its real epilogue) vs torch.matmul on the same M x K x N.
 

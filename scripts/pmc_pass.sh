@@ -5,11 +5,12 @@ set -o pipefail
 tag=${1:-pmc}
 nw=${2:-48}
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}  # where the logs and traces go
+mkdir -p $OUT
 B="scripts/pmc_step.py $nw 3"
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -s KILL 240 rocprofv3 --pmc $c --output-format csv -d gpurun_out/${tag}_$c -o run -- python3 $B > gpurun_out/${tag}_$c.log 2>&1
-  rc=$?; echo "pmc $c rc=$rc"; [ $rc -ne 0 ] && { tail -5 gpurun_out/${tag}_$c.log; exit $rc; }
+  timeout -s KILL 240 rocprofv3 --pmc $c --output-format csv -d $OUT/${tag}_$c -o run -- python3 $B > $OUT/${tag}_$c.log 2>&1
+  rc=$?; echo "pmc $c rc=$rc"; [ $rc -ne 0 ] && { tail -5 $OUT/${tag}_$c.log; exit $rc; }
 done
-python3 scripts/pmc_traffic.py gpurun_out/${tag}_FETCH_SIZE gpurun_out/${tag}_WRITE_SIZE gpurun_out/${tag}_traffic.json
-python3 scripts/pmc_per_kernel.py gpurun_out/${tag}_FETCH_SIZE gpurun_out/${tag}_WRITE_SIZE 60 > gpurun_out/${tag}_per_kernel.txt
+python3 scripts/pmc_traffic.py $OUT/${tag}_FETCH_SIZE $OUT/${tag}_WRITE_SIZE $OUT/${tag}_traffic.json
+python3 scripts/pmc_per_kernel.py $OUT/${tag}_FETCH_SIZE $OUT/${tag}_WRITE_SIZE 60 > $OUT/${tag}_per_kernel.txt

@@ -39,6 +39,38 @@ def test_spawned_ranks_gather_in_clip_order(n):
     assert res["scaling"] == "weak" and res["config"]["global_batch"] == n * res["config"]["windows_per_batch"] * 16
 
 
+def test_dump_outputs_writes_the_last_step(tmp_path):
+    """--dump-outputs: rank 0's last timed step (windows 4 and 5 of its 3 x 2) as float32
+    .npy files, identical from run to run."""
+    import numpy as np
+    runs = []
+    for d in ("a", "b"):
+        r = _bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d))
+        assert r.returncode == 0, r.stderr
+        assert _line(r)["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / d)) == ["frames.npy", "frames_u8.npy"]
+        runs.append({n: np.load(tmp_path / d / f"{n}.npy") for n in ("frames", "frames_u8")})
+    a, b = runs
+    assert a["frames"].dtype == np.float32 and a["frames_u8"].dtype == np.float32
+    assert a["frames"].shape == (2, 16, 3, 8, 8) and a["frames_u8"].shape == (2, 16, 8, 8, 3)
+    assert (a["frames_u8"][0] == 4).all() and (a["frames_u8"][1] == 5).all()
+    assert np.array_equal(a["frames"], b["frames"]) and np.array_equal(a["frames_u8"], b["frames_u8"])
+
+
+def test_dump_outputs_samples_a_large_array(tmp_path):
+    """An array above DUMP_MAX_ELEMS is written as the same seeded, sorted sample every time."""
+    import numpy as np
+    import torch
+
+    import bench
+    x = torch.arange(bench.DUMP_MAX_ELEMS + 7, dtype=torch.float32).view(-1, 1)  # exact in fp32: value == index
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x})
+    a, b = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_ELEMS,) and np.array_equal(a, b)
+    assert (np.diff(a) >= 0).all() and a[0] >= 0 and a[-1] < x.numel() and len(np.unique(a)) > a.size // 2
+
+
 def test_torchrun_style_worker_env():
     """Under torchrun the process is already a worker: WORLD_SIZE must match --gpus."""
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT="1")
