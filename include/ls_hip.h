@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define LS_ABI_VERSION 13
+#define LS_ABI_VERSION 14
 
 typedef enum {
   LS_OK = 0,
@@ -465,6 +465,17 @@ int ls_audio_chunks(const uint16_t* feat, int64_t ld_row, int32_t T, int32_t lay
  * out uint8 HWC [N][out_h][out_w][3]. */
 int ls_face_resize_u8(const float* faces, int32_t N, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w,
                       uint8_t* out, void* stream);
+
+/* ImageProcessor.resize on the ingest side (image_processor.py:42-44, 145-152; ABI 14):
+ * torchvision's v1 transforms.Resize((out_h, out_w), BILINEAR, antialias=True) of a
+ * uint8 face = cast to float, aten _upsample_bilinear2d_aa (width pass, then height
+ * pass, float intermediate), torch.round (half to even), clamp to 0..255, uint8.
+ * src uint8 NCHW [N][3][in_h][in_w] (data.pth "faces"); dst uint8 NCHW
+ * [N][3][out_h][out_w].  A dimension that already matches is copied through.
+ * LS_ERR_INVALID, nothing launched: null pointers, non-positive sizes, a downscale
+ * factor above 7 in either dimension (the filter's taps are held in 16 registers). */
+int ls_resize_faces_u8(const uint8_t* src, int32_t N, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w,
+                       uint8_t* dst, void* stream);
 
 /* Constant tables of the warp (OpenCV initInterTab2D Lanczos4 fixed-point coefficients,
  * getGaussianKernel(2 w + 1, 0) for w = 0..w_edge_max), computed on the host and copied

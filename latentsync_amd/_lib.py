@@ -10,7 +10,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LS_HIP_LIB", os.path.join(HERE, "libls_hip.so"))
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 
@@ -128,6 +128,7 @@ _SIGS = {
     "ls_audio_chunks": (C.c_int, [c_vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                   C.c_int32, C.c_int32, c_vp, C.c_int32, c_vp]),
     "ls_face_resize_u8": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_vp, c_vp]),
+    "ls_resize_faces_u8": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_vp, c_vp]),
     "ls_restore_tables_bytes": (C.c_size_t, [C.c_int32]),
     "ls_restore_init_tables": (C.c_int, [c_vp, C.c_int32, c_vp]),
     "ls_restore_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

@@ -183,7 +183,7 @@ __global__ void __launch_bounds__(512, 1) ff_fused_kernel(FFArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------
-// ff_chain_kernel (round 6, ABI 14 ls_ff_chain): the 32x32-level tail of a Transformer3D /
+// ff_chain_kernel (round 6, ABI 13 ls_ff_chain): the 32x32-level tail of a Transformer3D /
 // motion block in ONE launch -- the attention branch's out-projection + residual, the
 // LayerNorm, the GEGLU FeedForward + residual, proj_out + the block input, and the
 // GroupNorm column sums of the result for the next GroupNorm:

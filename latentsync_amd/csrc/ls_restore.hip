@@ -257,6 +257,50 @@ __global__ void __launch_bounds__(256) face_resize_kernel(const float* __restric
   o[0] = res[0]; o[1] = res[1]; o[2] = res[2];
 }
 
+// The ingest side of the same filter: ImageProcessor.resize (image_processor.py:42-44,
+// transforms.Resize((R, R), BILINEAR, antialias=True)) on a uint8 face.  torchvision's
+// v1 Resize casts the uint8 tensor to float, interpolates (width pass, then height pass,
+// the intermediate float and unrounded), torch.round()s (half to even) and casts back.
+// Planar in and out, (N,3,H,W): a row of 64 threads reads and writes consecutive bytes
+// of one plane.  A dimension that already matches is copied through, not filtered.
+__global__ void __launch_bounds__(256) resize_faces_u8_kernel(const uint8_t* __restrict__ src, int in_h, int in_w,
+                                                              int out_h, int out_w, uint8_t* __restrict__ dst) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const int n = blockIdx.z;
+  if (x >= out_w || y >= out_h) return;
+  float wx[AA_MAXT], wy[AA_MAXT];
+  int x0, y0, nx, ny;
+  const bool hpass = in_w != out_w, vpass = in_h != out_h;
+  if (hpass) {
+    nx = aa_weights(x, in_w, out_w, wx, &x0);
+  } else {
+    nx = 1; x0 = x; wx[0] = 1.f;
+  }
+  if (vpass) {
+    ny = aa_weights(y, in_h, out_h, wy, &y0);
+  } else {
+    ny = 1; y0 = y; wy[0] = 1.f;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const uint8_t* plane = src + ((long)n * 3 + c) * in_h * in_w;
+    float v = 0.f;
+    for (int j = 0; j < ny; ++j) {
+      const uint8_t* row = plane + (long)(y0 + j) * in_w + x0;
+      float h = (float)row[0];
+      if (hpass) {
+        h = (float)row[0] * wx[0];
+        for (int i = 1; i < nx; ++i) h = fmaf((float)row[i], wx[i], h);
+      }
+      if (!vpass) v = h;
+      else v = j == 0 ? h * wy[0] : fmaf(h, wy[j], v);
+    }
+    const float r = fminf(fmaxf(rintf(v), 0.f), 255.f);
+    dst[(((long)n * 3 + c) * out_h + y) * out_w + x] = (uint8_t)(int)r;
+  }
+}
+
 // mask_e = erode2x2(warpAffine(ones)) over the ROI (affine_transform.py:96-100), and
 // area[n] += sum(mask_e) (fp64; the reference sums in float32).
 __global__ void __launch_bounds__(256) restore_mask_kernel(const double* __restrict__ warp,
@@ -575,6 +619,23 @@ int ls_face_resize_u8(const float* faces, int32_t N, int32_t in_h, int32_t in_w,
   hipLaunchKernelGGL(face_resize_kernel, dim3(cdiv(out_w, 64), cdiv(out_h, 4), N), dim3(256), 0,
                      (hipStream_t)stream, faces, in_h, in_w, out_h, out_w, out);
   return check_launch("face_resize_kernel");
+}
+
+int ls_resize_faces_u8(const uint8_t* src, int32_t N, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w,
+                       uint8_t* dst, void* stream) {
+  if (!src || !dst || N < 0 || in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0)
+    return fail(LS_ERR_INVALID, "ls_resize_faces_u8: bad args");
+  // support taps: ceil(2 * max(scale, 1)) + 1 must fit AA_MAXT
+  if ((double)in_w / out_w > (AA_MAXT - 2) / 2.0 || (double)in_h / out_h > (AA_MAXT - 2) / 2.0)
+    return fail(LS_ERR_INVALID, "ls_resize_faces_u8: downscale factor above 7");
+  // one image per grid z-slice: at most 65535 of them per launch
+  for (int32_t n0 = 0; n0 < N; n0 += 65535) {
+    const int32_t nb = N - n0 < 65535 ? N - n0 : 65535;
+    hipLaunchKernelGGL(resize_faces_u8_kernel, dim3(cdiv(out_w, 64), cdiv(out_h, 4), nb), dim3(256), 0,
+                       (hipStream_t)stream, src + (size_t)n0 * 3 * in_h * in_w, in_h, in_w, out_h, out_w,
+                       dst + (size_t)n0 * 3 * out_h * out_w);
+  }
+  return N == 0 ? LS_OK : check_launch("resize_faces_u8_kernel");
 }
 
 size_t ls_restore_workspace_bytes(int32_t N, int32_t roi_h, int32_t roi_w) {

@@ -479,6 +479,28 @@ def ddim_cfg_step(eps, Bu, guidance, lat, coef, step, unet_in):
                                _p(unet_in), unet_in.shape[-1], _stream()), "ls_ddim_cfg_step")
 
 
+def resize_faces_u8(src, out_h, out_w, out=None):
+    """ImageProcessor.resize (image_processor.py:42-44) of uint8 faces (N,3,H,W) ->
+    (N,3,out_h,out_w) uint8: torchvision's antialiased bilinear Resize with its
+    round-half-even back to uint8.  ``out`` is a caller's static buffer."""
+    lib = _lib.load()
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[1] != 3 or not src.is_cuda:
+        raise ValueError(f"resize_faces_u8: uint8 (N,3,H,W) on the device expected, got {src.dtype} "
+                         f"{tuple(src.shape)} on {src.device}")
+    if not src.is_contiguous():
+        raise ValueError("resize_faces_u8: src must be contiguous")
+    N, _, Hi, Wi = src.shape
+    out_h, out_w = int(out_h), int(out_w)
+    if out is None:
+        out = torch.empty((N, 3, out_h, out_w), dtype=torch.uint8, device=src.device)
+    elif (out.dtype != torch.uint8 or tuple(out.shape) != (N, 3, out_h, out_w) or out.device != src.device or
+          not out.is_contiguous()):
+        raise ValueError(f"resize_faces_u8: out must be contiguous uint8 {(N, 3, out_h, out_w)} on {src.device}")
+    if N:
+        check(lib.ls_resize_faces_u8(_p(src), N, Hi, Wi, out_h, out_w, _p(out), _stream()), "ls_resize_faces_u8")
+    return out
+
+
 def prep_pixels(faces_u8, mask, ld=8, pix=None, masked=None):
     lib = _lib.load()
     F_, _, R, _ = faces_u8.shape

@@ -5,7 +5,8 @@ The per-window hot loop (lipsync_pipeline.py:500-575) runs in ``WindowEngine``:
 every tensor of a window is device-resident in static buffers, and the window is
 three captured hipGraphs replayed back to back --
 
-  encode : pixel prep (ImageProcessor.preprocess_fixed_mask_image) -> VAE encode
+  encode : (faces stored at another resolution: ImageProcessor.resize ->) pixel
+           prep (ImageProcessor.preprocess_fixed_mask_image) -> VAE encode
            of masked + reference faces -> posterior sample * 0.18215 -> pack the
            13-channel UNet input (prepare_mask_latents / prepare_image_latents,
            :284-320, :547-549), reset the device step counter
@@ -128,7 +129,7 @@ class WindowEngine:
     """Device-resident executor of one 16-frame window; see module docstring."""
 
     def __init__(self, unet, vae, scheduler, num_frames=16, resolution=256, num_inference_steps=20,
-                 guidance_scale=1.0, use_graphs=True, audio_tokens=50, windows=1):
+                 guidance_scale=1.0, use_graphs=True, audio_tokens=50, windows=1, face_resolution=None):
         self.unet, self.vae, self.scheduler = unet, vae, scheduler
         self.ud = unet._require_device()
         self.vd = vae._require()
@@ -151,6 +152,11 @@ class WindowEngine:
         cd = unet.config.cross_attention_dim
         z = lambda *s, dt=torch.bfloat16: torch.zeros(s, dtype=dt, device=dev)
         self.faces = z(F_, 3, R, R, dt=torch.uint8)
+        # Faces stored at another resolution S (a data.pth cut at 512^2 served by a 256^2
+        # model): they are staged here and ImageProcessor.resize (image_processor.py:42-44,
+        # 145-152) runs as the first node of the encode graph.  None = the faces arrive at R.
+        S = R if face_resolution is None else int(face_resolution)
+        self.faces_src = z(F_, 3, S, S, dt=torch.uint8) if S != R else None
         self.mask = z(R, R, dt=torch.float32)
         self.audio = z(Bu * F_ * audio_tokens, cd)
         self.init_lat = z(P, 4, dt=torch.float32)
@@ -171,6 +177,8 @@ class WindowEngine:
 
     # -- the three phases --------------------------------------------------------
     def _encode(self):
+        if self.faces_src is not None:
+            ops.resize_faces_u8(self.faces_src, self.R, self.R, out=self.faces)
         ops.prep_pixels(self.faces, self.mask, 8, self.pix, self.masked)
         mom = self.vd.encode_moments(self.masked)
         ops.vae_sample(mom, self.eps_m, SCALING, 0.0, self.cond, 5)
@@ -238,11 +246,16 @@ class WindowEngine:
     # -- inputs / execution -------------------------------------------------------
     def load(self, faces_u8, mask, audio_chunks, init_latent, eps_masked, eps_ref):
         """Stage the inputs of `windows` consecutive windows into the static buffers.
-        faces (W*F,3,R,R) uint8; mask (R,R) keep-mask; audio (W*F,50,384);
+        faces (W*F,3,R,R) uint8 -- (W*F,3,S,S) for an engine built with
+        face_resolution=S; mask (R,R) keep-mask; audio (W*F,50,384);
         init_latent (W or 1, 4, 1 or F, h, w) (one draw per window, repeated over its
         frames as prepare_latents does); eps_* (W*F,4,h,w)."""
         F_, h = self.FT, self.h
-        self.faces.copy_(faces_u8)
+        stage = self.faces if self.faces_src is None else self.faces_src
+        if tuple(faces_u8.shape) != tuple(stage.shape):
+            raise ValueError(f"faces {tuple(faces_u8.shape)}: this engine takes {tuple(stage.shape)} "
+                             "(frames in flight, 3, face resolution, face resolution)")
+        stage.copy_(faces_u8)
         self.mask.copy_(mask)
         a = audio_chunks.reshape(F_ * self.L, -1).to(torch.bfloat16)
         if self.Bu == 2:  # torch.cat([zeros, audio]) (lipsync_pipeline.py:505-507)
@@ -357,8 +370,11 @@ class LipsyncPipeline:
             raise ValueError(f"`callback_steps` has to be a positive integer but is {callback_steps} of type"
                              f" {type(callback_steps)}.")
 
-    def engine(self, num_frames, resolution, steps, guidance_scale, use_graphs=True, windows=1):
-        key = (num_frames, resolution, steps, float(guidance_scale), use_graphs, windows)
+    def engine(self, num_frames, resolution, steps, guidance_scale, use_graphs=True, windows=1,
+               face_resolution=None):
+        if face_resolution is not None and int(face_resolution) == resolution:
+            face_resolution = None  # faces at the resolution: the plain engine, no resize node
+        key = (num_frames, resolution, face_resolution, steps, float(guidance_scale), use_graphs, windows)
         eng = self._engines.get(key)
         if eng is not None and (eng.unet is not self.denoising_unet or eng.ud is not self.denoising_unet._dev or
                                 eng.vae is not self.vae or eng.scheduler is not self.scheduler):
@@ -369,7 +385,8 @@ class LipsyncPipeline:
             while len(self._engines) >= max(1, int(self.max_engines)):
                 self._engines.popitem(last=False)[1].close()  # least recently used
             eng = self._engines[key] = WindowEngine(self.denoising_unet, self.vae, self.scheduler, num_frames,
-                                                    resolution, steps, guidance_scale, use_graphs, windows=windows)
+                                                    resolution, steps, guidance_scale, use_graphs, windows=windows,
+                                                    face_resolution=face_resolution)
         self._engines.move_to_end(key)
         return eng
 
@@ -387,15 +404,19 @@ class LipsyncPipeline:
         return lat.repeat(1, 1, num_frames, 1, 1) * self.scheduler.init_noise_sigma
 
     def run_windows(self, faces_u8, whisper_chunks, mask, num_frames=16, num_inference_steps=20, guidance_scale=1.5,
-                    generator=None, all_latents=None, vae_noise=None, callback=None, callback_steps=1):
+                    generator=None, all_latents=None, vae_noise=None, callback=None, callback_steps=1, height=None):
         """The hot loop (:489-575) over ceil(len(chunks)/num_frames) windows.
-        faces_u8 (N,3,R,R) (N >= #chunks, already repeated/truncated as the
-        reference does), whisper_chunks (n,50,384).  Window i covers frames
+        faces_u8 (N,3,S,S) (N >= #chunks, already repeated/truncated as the
+        reference does), whisper_chunks (n,50,384).  R = ``height`` or, by default, the
+        faces' own S; faces stored at another resolution are resized to R on the device,
+        window by window, inside the engine's encode graph (ImageProcessor.resize,
+        :512 -> image_processor.py:145-152).  Window i covers frames
         [i*num_frames, (i+1)*num_frames) of the n chunks; the last one is short
         when n % num_frames != 0 (force_video_length, :455, :500-511) and runs
         with its own frame count, as the reference's slices do.  Returns decoded +
         pasted frames (n, 3, R, R) fp32 and uint8 (n, R, R, 3) on device."""
-        R = faces_u8.shape[-1]
+        S = faces_u8.shape[-1]
+        R = height or S
         self.check_inputs(R, R, callback_steps)
         n = whisper_chunks.shape[0]
         if faces_u8.shape[0] < n:
@@ -424,10 +445,12 @@ class LipsyncPipeline:
         full = [i for i in mine if size[i] == num_frames]
         E, batches = plan_window_batches(full, 1 if callback is not None else self.windows_per_batch)
         batches = [(E, b) for b in batches] + [(1, [i]) for i in mine if size[i] < num_frames]
+        resize = {"face_resolution": S} if S != R else {}  # faces at R: the engine call of before
         res = {}
         for E, wins in batches:
             Fw = size[wins[0]]
-            eng = self.engine(Fw, R, num_inference_steps, guidance_scale, use_graphs=Fw == num_frames, windows=E)
+            eng = self.engine(Fw, R, num_inference_steps, guidance_scale, use_graphs=Fw == num_frames, windows=E,
+                              **resize)
             run = wins + [wins[-1]] * (E - len(wins))  # padding windows: computed, discarded
             sls = [slice(i * num_frames, i * num_frames + Fw) for i in run]
             cat = lambda xs: torch.cat([x.to(self.device) for x in xs])
@@ -509,8 +532,8 @@ class LipsyncPipeline:
         video_frames = None if (kwargs.get("faces_only") or not rank0) else read_video_frames(video_path)
         R = height or faces.shape[-1]
         self.check_inputs(R, width or R, callback_steps)
-        if faces.shape[-1] != R:
-            raise NotImplementedError("face resize needs torchvision (out of scope): store faces at the resolution")
+        # faces stored at another resolution are resized to R in run_windows, as the
+        # reference's preprocess_fixed_mask_image does for every window (:512)
         keep = load_fixed_mask(R, mask_image_path)
         from .audio import read_audio
         audio_samples = read_audio(audio_path, audio_sample_rate)
@@ -542,7 +565,7 @@ class LipsyncPipeline:
             per_frame(rep.truncate_to_length, len(chunks))
         chunks = torch.stack([c.to(self.device) for c in chunks])
         out, out_u8 = self.run_windows(faces, chunks, keep, num_frames, num_inference_steps, guidance_scale,
-                                       generator, callback=callback, callback_steps=callback_steps)
+                                       generator, callback=callback, callback_steps=callback_steps, height=R)
         if not rank0:
             return None  # rank 0 restores and writes the gathered clip
         frames_out = out_u8
