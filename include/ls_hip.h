@@ -450,6 +450,21 @@ size_t ls_log_mel_workspace_bytes(int64_t n_samples, int32_t n_mels);
 int ls_log_mel(const float* audio, int64_t n_samples, const float* filters, int32_t n_mels, int64_t t_pad,
                uint16_t* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Sample-rate conversion by the rational factor L / M (sr_out / sr_in in lowest terms)
+ * with a polyphase FIR: what ffmpeg does for the reference's read_audio (util.py:103-112)
+ * and whisper's load_audio (whisper/audio.py:22-50).  x fp32 [n_in] mono; taps fp32
+ * [L][2 * half + 1], row p = the filter of phase p (latentsync_amd.audio.resample_taps);
+ * y fp32 [n_out], n_out = ceil(n_in * L / M).  Output n lies at input time n * M / L:
+ *   base = (n * M) / L, p = (n * M) % L,
+ *   y[n] = sum_{j = -half..half} taps[p][j + half] * x[base + j],  x = 0 outside [0, n_in)
+ * (64-bit index arithmetic, zero padding by predicate, fp32 accumulation).  No
+ * allocation, no synchronisation, capturable.  LS_ERR_INVALID, nothing launched: null
+ * pointers, L, M, half or n_in < 1, n_out != ceil(n_in * L / M), L or M >= 2^22,
+ * n_in > 2^40, or 255 * M / L + 2 * half + 2 > 16384 (the input window of one
+ * 256-output block is staged in 64 KiB of LDS: M / L up to about 50). */
+int ls_resample(const float* x, int64_t n_in, const float* taps, int32_t L, int32_t M, int32_t half, float* y,
+                int64_t n_out, void* stream);
+
 /* Audio2Feature.feature2chunks / get_sliced_feature (audio2feature.py:24-49, 85-100):
  * feat bf16 rows [T][layers][C] with row stride ld_row; chunk i, row j =
  * feat[clamp(int(i * 50 / fps) - 2 * left + j / layers, 0, T - 1)][j % layers];

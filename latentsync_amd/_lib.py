@@ -125,6 +125,7 @@ _SIGS = {
     "ls_gemm_occupancy": (C.c_int, [C.c_int32]),
     "ls_log_mel_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "ls_log_mel": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int32, C.c_int64, c_vp, c_vp, C.c_size_t, c_vp]),
+    "ls_resample": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, C.c_int64, c_vp]),
     "ls_audio_chunks": (C.c_int, [c_vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                   C.c_int32, C.c_int32, c_vp, C.c_int32, c_vp]),
     "ls_face_resize_u8": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_vp, c_vp]),

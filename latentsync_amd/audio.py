@@ -1,6 +1,8 @@
 """Audio2Feature -- drop-in for latentsync/whisper/audio2feature.py:9-135 with the
 Whisper-tiny encoder on the HIP path.
 
+  WAV file --read_wav (host: RIFF walk, PCM / float decode, mean over channels)-->
+      fp32 mono at the file's rate --ls_resample (only if that rate is not 16 kHz)-->
   wave (16 kHz fp32) --ls_log_mel--> bf16 mel [n_seg*3000][80] (frame-major,
       zero pad per 30 s segment: transcribe.py's segment loop + pad_or_trim)
   --conv1 (k3, GELU)--> --conv2 (k3 s2, GELU)--> + positional embedding
@@ -20,10 +22,11 @@ Conv1d runs as the 3x3 implicit-GEMM conv on a 1-row image (kernel on the middle
 row, packing.pack_weight).  All arithmetic is in libls_hip.so; there is no CPU
 path.
 """
+import functools
 import math
 import os
+import struct
 import types
-import wave
 
 import numpy as np
 import torch
@@ -70,24 +73,164 @@ def mel_filters(sr=SAMPLE_RATE, n_fft=N_FFT, n_mels=80):
     return (weights * enorm[:, None]).astype(np.float32)
 
 
+WAVE_FORMAT_PCM, WAVE_FORMAT_IEEE_FLOAT, WAVE_FORMAT_EXTENSIBLE = 0x0001, 0x0003, 0xFFFE
+_FORMAT_NAMES = {0x0002: "MS ADPCM", 0x0006: "A-law", 0x0007: "mu-law", 0x0011: "IMA ADPCM", 0x0031: "GSM 6.10",
+                 0x0055: "MPEG layer 3"}
+
+
+def _compressed_signature(head):
+    """Name of the compressed container the first bytes of a file belong to, or None."""
+    if head[:3] == b"ID3" or (len(head) >= 2 and head[0] == 0xFF and (head[1] & 0xE0) == 0xE0):
+        return "mp3"
+    if head[:4] == b"OggS":
+        return "ogg"
+    if head[4:8] == b"ftyp":
+        return "mp4 / m4a"
+    return None
+
+
+def _decode_pcm(raw, tag, bits, path):
+    """Interleaved little-endian samples -> fp32 in [-1, 1): u8 (u - 128) / 128,
+    s16 / 2^15, s24 / 2^23, s32 / 2^31, float 32 / 64 as stored."""
+    if tag == WAVE_FORMAT_PCM:
+        if bits == 8:
+            return (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
+        if bits == 16:
+            return np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
+        if bits == 24:
+            b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+            v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+            return ((v ^ 0x800000) - 0x800000).astype(np.float32) / 8388608.0
+        if bits == 32:
+            return np.frombuffer(raw, dtype="<i4").astype(np.float32) / 2147483648.0
+    elif bits in (32, 64):
+        return np.frombuffer(raw, dtype="<f4" if bits == 32 else "<f8").astype(np.float32)
+    kind = "PCM" if tag == WAVE_FORMAT_PCM else "IEEE float"
+    raise ValueError(f"{path}: {bits}-bit {kind} samples are not supported")
+
+
+def read_wav(path):
+    """RIFF/WAVE file -> (fp32 mono samples, sample rate).  PCM u8 / s16 / s24 / s32 and
+    IEEE float 32 / 64, plain or WAVE_FORMAT_EXTENSIBLE (resolved through the first two
+    bytes of its sub-format GUID; the container width scales, not wValidBitsPerSample),
+    any channel count (fp32 mean over the channels, ffmpeg's stereo -> mono).  Unknown
+    chunks are skipped with their pad byte; a `data` size of 0 or 0xFFFFFFFF (a streamed
+    file) or one past the end of the file means "to the end of the file", whole frames
+    only.  Host only: nothing here touches the GPU."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    if buf[:4] != b"RIFF" or buf[8:12] != b"WAVE":
+        kind = _compressed_signature(buf[:12])
+        if kind:
+            raise ValueError(f"{path}: not a RIFF/WAVE file, it looks like {kind}: compressed audio is out of "
+                             "scope (decode it to WAV first)")
+        what = f"a RIFF file of form type {buf[8:12]!r}" if buf[:4] == b"RIFF" else "no RIFF header"
+        raise ValueError(f"{path}: not a RIFF/WAVE file ({what})")
+    fmt = None
+    pos = 12
+    while pos + 8 <= len(buf):
+        cid, size = buf[pos:pos + 4], int.from_bytes(buf[pos + 4:pos + 8], "little")
+        body = pos + 8
+        if cid == b"fmt ":
+            if size < 16 or body + size > len(buf):
+                raise ValueError(f"{path}: truncated fmt chunk ({size} bytes)")
+            tag, ch, rate, _, _, bits = struct.unpack_from("<HHIIHH", buf, body)
+            if tag == WAVE_FORMAT_EXTENSIBLE:
+                if size < 40:
+                    raise ValueError(f"{path}: WAVE_FORMAT_EXTENSIBLE with a {size}-byte fmt chunk (40 expected)")
+                tag = struct.unpack_from("<H", buf, body + 24)[0]
+            fmt = (tag, ch, rate, bits)
+        elif cid == b"data":
+            if fmt is None:
+                raise ValueError(f"{path}: no fmt chunk before the data chunk")
+            tag, ch, rate, bits = fmt
+            if tag not in (WAVE_FORMAT_PCM, WAVE_FORMAT_IEEE_FLOAT):
+                name = _FORMAT_NAMES.get(tag)
+                raise ValueError(f"{path}: unsupported wFormatTag 0x{tag:04X}" + (f" ({name})" if name else "") +
+                                 ": only PCM and IEEE float WAV are read")
+            if ch < 1:
+                raise ValueError(f"{path}: fmt chunk declares zero channels")
+            if rate < 1:
+                raise ValueError(f"{path}: fmt chunk declares a zero sample rate")
+            if bits % 8 or bits == 0:
+                raise ValueError(f"{path}: {bits}-bit samples are not supported")
+            if size in (0, 0xFFFFFFFF) or body + size > len(buf):
+                size = len(buf) - body
+            frame = ch * (bits // 8)
+            a = _decode_pcm(buf[body:body + size // frame * frame], tag, bits, path)
+            if ch > 1:
+                a = a.reshape(-1, ch).mean(1)
+            return a, rate
+        pos = body + size + (size & 1)
+    raise ValueError(f"{path}: no {'data' if fmt else 'fmt'} chunk")
+
+
+# ----------------------------------------------------------------- sample-rate conversion
+
+RESAMPLE_ZEROS, RESAMPLE_ROLLOFF, RESAMPLE_BETA = 32, 0.95, 9.0
+
+
+@functools.lru_cache(maxsize=8)
+def _resample_design(sr_in, sr_out):
+    g = math.gcd(sr_in, sr_out)
+    L, M = sr_out // g, sr_in // g
+    fc = min(1.0, L / M) * RESAMPLE_ROLLOFF
+    half = math.ceil(RESAMPLE_ZEROS / fc)
+    tau = np.arange(L, dtype=np.float64)[:, None] / L - np.arange(-half, half + 1, dtype=np.float64)[None, :]
+    u = tau * fc / RESAMPLE_ZEROS
+    kaiser = np.where(np.abs(u) <= 1.0, np.i0(RESAMPLE_BETA * np.sqrt(np.maximum(1.0 - u * u, 0.0))) /
+                      np.i0(RESAMPLE_BETA), 0.0)
+    h = fc * np.sinc(fc * tau) * kaiser
+    h /= h.sum(axis=1, keepdims=True)
+    h32 = h.astype(np.float32)
+    h.setflags(write=False)
+    h32.setflags(write=False)
+    return L, M, half, h32, h
+
+
+def _check_rates(sr_in, sr_out):
+    if int(sr_in) != sr_in or int(sr_out) != sr_out or sr_in < 1 or sr_out < 1:
+        raise ValueError(f"sample rates must be positive integers, got {sr_in} and {sr_out}")
+    return int(sr_in), int(sr_out)
+
+
+def resample_taps(sr_in, sr_out):
+    """(L, M, half, taps) of the sr_in -> sr_out polyphase resampler (ls_resample):
+    L / M = sr_out / sr_in in lowest terms; taps fp32 [L][2 * half + 1], row p the
+    filter of phase p.  A Kaiser-windowed sinc (beta 9, 32 zero crossings per side,
+    cutoff 0.95 of the lower Nyquist rate), h[p, j] = fc sinc(fc tau) w(tau fc / 32) at
+    tau = p / L - j, every row divided by its sum (unit DC gain at every phase).  Designed
+    in float64 (`resample_taps64`), cached per rate pair."""
+    return _resample_design(*_check_rates(sr_in, sr_out))[:4]
+
+
+def resample_taps64(sr_in, sr_out):
+    """The float64 table `resample_taps` rounds to fp32."""
+    return _resample_design(*_check_rates(sr_in, sr_out))[4]
+
+
+def resampled_length(n_in, sr_in, sr_out):
+    """ceil(n_in * L / M)."""
+    g = math.gcd(sr_in, sr_out)
+    return -(-n_in * (sr_out // g) // (sr_in // g))
+
+
 def load_wav(path, sr=SAMPLE_RATE):
-    """16-bit PCM WAV -> fp32 mono in [-1, 1).  Stands in for whisper's ffmpeg
-    load_audio (audio.py:22-50); other containers / resampling need ffmpeg,
-    which is outside this build."""
-    with wave.open(path, "rb") as f:
-        if f.getsampwidth() != 2:
-            raise NotImplementedError(f"{path}: only 16-bit PCM WAV is supported (decode with ffmpeg first)")
-        if f.getframerate() != sr:
-            raise NotImplementedError(f"{path}: sample rate {f.getframerate()} != {sr} (resample with ffmpeg first)")
-        ch = f.getnchannels()
-        a = np.frombuffer(f.readframes(f.getnframes()), dtype="<i2").astype(np.float32) / 32768.0
-    if ch > 1:
-        a = a.reshape(-1, ch).mean(1)
-    return a
+    """WAV -> fp32 mono at `sr` on the host.  Stands in for whisper's ffmpeg load_audio
+    (audio.py:22-50): `read_wav` decodes on the host, and a file at another rate goes
+    through the device resampler (ops.resample); there is no CPU resampling path."""
+    a, file_sr = read_wav(path)
+    if file_sr == sr or a.size == 0:
+        return a
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{path}: the {file_sr} Hz -> {sr} Hz resampler runs on the HIP device, and none is "
+                           "available")
+    return ops.resample(torch.from_numpy(a), file_sr, sr).cpu().numpy()
 
 
 def read_audio(audio_path, audio_sample_rate=SAMPLE_RATE):
-    """utils/util.py:103-112 (mono float samples)."""
+    """utils/util.py:103-112: mono float samples at `audio_sample_rate`, whatever the
+    file's own rate and channel count."""
     if audio_path is None:
         raise ValueError("Audio path is required.")
     return torch.from_numpy(load_wav(audio_path, audio_sample_rate))
@@ -246,8 +389,13 @@ class Audio2Feature:
         return X, T50
 
     def _audio2feat(self, audio):
-        if isinstance(audio, str):
-            audio = load_wav(audio)
+        if isinstance(audio, (str, os.PathLike)):
+            # Whisper sees 16 kHz whatever the file's rate (whisper/audio.py:22-50); the
+            # resampled samples stay on the device for log_mel
+            audio, file_sr = read_wav(audio)
+            if file_sr != SAMPLE_RATE:
+                self._require()
+                audio = ops.resample(torch.from_numpy(audio).to(self.device), file_sr, SAMPLE_RATE)
         X, T50 = self.encode_stacked(audio)
         feat = X[:T50].float()
         self._last = (feat, X[:T50])

@@ -16,6 +16,9 @@
 //  * audio_chunks_kernel: Audio2Feature.get_sliced_feature / feature2chunks
 //    (audio2feature.py:24-49, 85-100): chunk i row j = feature[clamp(c-2L+j/layers)]
 //    [layer j%layers], c = int(i * 50 / fps) evaluated in double like Python.
+//  * resample_kernel: polyphase FIR sample-rate conversion of the decoded WAV to the
+//    16 kHz the mel front end expects (the job ffmpeg does for the reference's
+//    read_audio / whisper load_audio).
 #include "ls_common.h"
 
 namespace ls {
@@ -134,6 +137,44 @@ __global__ void audio_chunks_kernel(const u16* __restrict__ feat, long ld_row, i
   }
 }
 
+// Polyphase FIR sample-rate conversion by L / M (audio.resample_taps).  Output n lies at
+// input time n * M / L: base = (n * M) / L, phase p = (n * M) % L, y[n] = sum_j
+// taps[p][j + half] * x[base + j], j in [-half, half], x zero outside [0, n_in).  One
+// block owns RS_BLK consecutive outputs.  Their input window (at most
+// (RS_BLK - 1) * M / L + 2 * half + 2 samples, the zero padding applied by predicate as it
+// is staged) sits in LDS: neighbouring outputs read overlapping runs of it, 2 * half + 1
+// times each.  A block touches min(L, RS_BLK) rows of the phase table, every element of a
+// row exactly once, so the table is read through the cache (the rows of one wave stay
+// resident across its tap loop; the whole table is a few hundred KB of L2).  n * M
+// exceeds 2^31 from 304 s of 44.1 kHz audio on: all sample indices are 64-bit.
+constexpr int RS_BLK = 256;
+constexpr long RS_MAX_WINDOW = 16384;  // floats: 64 KiB of LDS per block
+
+__global__ void __launch_bounds__(RS_BLK)
+resample_kernel(const float* __restrict__ x, long n_in, const float* __restrict__ taps, int L, int M, int half,
+                float* __restrict__ y, long n_out, int window) {
+  extern __shared__ float rs_xs[];
+  const long n0 = (long)blockIdx.x * RS_BLK;
+  const long base0 = n0 * M / L;
+  for (int i = threadIdx.x; i < window; i += RS_BLK) {
+    const long idx = base0 - half + i;
+    rs_xs[i] = (idx >= 0 && idx < n_in) ? x[idx] : 0.f;
+  }
+  __syncthreads();
+  const long n = n0 + threadIdx.x;
+  if (n >= n_out) return;
+  const long t = n * M;
+  const long base = t / L;
+  const int p = (int)(t - base * L);
+  const int T = 2 * half + 1;
+  const float* h = taps + (long)p * T;
+  const float* xs = rs_xs + (int)(base - base0);  // xs[k] = x[base - half + k]
+  float acc = 0.f;
+#pragma unroll 4
+  for (int k = 0; k < T; ++k) acc = fmaf(h[k], xs[k], acc);
+  y[n] = acc;
+}
+
 }  // namespace ls
 
 using namespace ls;
@@ -173,4 +214,27 @@ extern "C" int ls_audio_chunks(const uint16_t* feat, int64_t ld_row, int32_t T, 
   audio_chunks_kernel<<<(int)std::min<long>(cdiv(n, 256), 8192), 256, 0, (hipStream_t)stream>>>(
       feat, ld_row, T, layers, C, n_chunks, fps, left, right, out, out_f32);
   return check_launch("audio_chunks_kernel");
+}
+
+extern "C" int ls_resample(const float* x, int64_t n_in, const float* taps, int32_t L, int32_t M, int32_t half,
+                           float* y, int64_t n_out, void* stream) {
+  if (!x || !taps || !y) return fail(LS_ERR_INVALID, "ls_resample: null pointer");
+  if (L < 1 || M < 1 || half < 1 || n_in < 1)
+    return fail(LS_ERR_INVALID, "ls_resample: L, M, half and n_in must be >= 1");
+  // n_in * L and n_out * M stay below 2^63
+  if (n_in > (int64_t)1 << 40 || L >= 1 << 22 || M >= 1 << 22 || half > 1 << 20)
+    return fail(LS_ERR_INVALID, "ls_resample: n_in above 2^40, L or M above 2^22, or half above 2^20");
+  const long want = ((long)n_in * L + M - 1) / M;
+  if (n_out != want)
+    return fail(LS_ERR_INVALID, "ls_resample: n_out " + std::to_string(n_out) + " != ceil(n_in * L / M) = " +
+                                    std::to_string(want));
+  const long window = ((long)(RS_BLK - 1) * M + L - 1) / L + 2L * half + 2;
+  if (window > RS_MAX_WINDOW)
+    return fail(LS_ERR_INVALID, "ls_resample: the input window of one block (" + std::to_string(window) +
+                                    " samples) exceeds 64 KiB of LDS: M / L too large");
+  const long blocks = (n_out + RS_BLK - 1) / RS_BLK;
+  if (blocks > 0x7fffffffL) return fail(LS_ERR_INVALID, "ls_resample: n_out too large for one grid");
+  resample_kernel<<<(unsigned)blocks, RS_BLK, (size_t)window * sizeof(float), (hipStream_t)stream>>>(
+      x, n_in, taps, L, M, half, y, n_out, (int)window);
+  return check_launch("resample_kernel");
 }

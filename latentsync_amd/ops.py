@@ -501,6 +501,35 @@ def resize_faces_u8(src, out_h, out_w, out=None):
     return out
 
 
+_RESAMPLE_TAPS = {}  # (sr_in, sr_out, device index) -> (L, M, half, device taps)
+
+
+def resample(x, sr_in, sr_out):
+    """Mono fp32 samples at sr_in -> ceil(n * L / M) samples at sr_out as a device fp32
+    tensor (ls_resample with audio.resample_taps' filter).  x: a 1-D tensor or array, on
+    the host or the device.  Equal rates return x itself, with no launch."""
+    if sr_in == sr_out:
+        return x
+    from .audio import resample_taps
+    lib = _lib.load()
+    x = torch.as_tensor(x)
+    if x.dim() != 1 or x.numel() < 1:
+        raise ValueError(f"resample: a non-empty 1-D signal expected, got shape {tuple(x.shape)}")
+    device = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    x = x.to(device, torch.float32).contiguous()
+    key = (int(sr_in), int(sr_out), device.index)
+    if key not in _RESAMPLE_TAPS:
+        L, M, half, taps = resample_taps(sr_in, sr_out)
+        _RESAMPLE_TAPS[key] = (L, M, half, torch.tensor(taps, device=device))
+    L, M, half, taps = _RESAMPLE_TAPS[key]
+    n_in = x.numel()
+    n_out = -(-n_in * L // M)
+    y = torch.empty(n_out, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        check(lib.ls_resample(_p(x), n_in, _p(taps), L, M, half, _p(y), n_out, _stream()), "ls_resample")
+    return y
+
+
 def prep_pixels(faces_u8, mask, ld=8, pix=None, masked=None):
     lib = _lib.load()
     F_, _, R, _ = faces_u8.shape

@@ -500,7 +500,11 @@ class LipsyncPipeline:
         uint8 (N,H,W,3) ``.npy`` or an ``.npz`` with a ``frames`` array
         (read_video's output, util.py:46-100).  The synced faces are pasted back into
         those frames on the GPU (restore_video, :577) and the result is written as an
-        .npz of the restored frames (uint8) plus the aligned audio.  With
+        .npz of the restored frames (uint8) plus the aligned audio.  ``audio_path`` is
+        any PCM or IEEE-float WAV, at any sample rate and channel count: it is decoded
+        on the host and converted to mono at ``audio_sample_rate`` (for the .npz) and at
+        16 kHz (for Whisper) on the device, as ffmpeg does for the reference
+        (util.py:103-112, whisper/audio.py:22-50); compressed audio is out of scope.  With
         ``faces_only=True`` (or a video_path that is not an array file) the
         lip-synced aligned faces are written instead and no warp-back happens."""
         from . import repeat as rep

@@ -73,7 +73,10 @@ def resolve_paths(p: dict, data_dir: str):
 
 def fetch_audio(url: str, dest: str):
     """download_file (download.py:6-40) for the sources this build can reach: a local
-    path or a file:// URL.  Network URLs are out of scope (no egress)."""
+    path or a file:// URL.  Network URLs are out of scope (no egress).  The file is
+    copied as it is: the pipeline takes any PCM or float WAV (TTS output at 22.05, 24,
+    44.1 or 48 kHz included) and resamples it on the device (audio.read_wav,
+    ops.resample); a compressed file is refused there with a ValueError."""
     src = url[len("file://"):] if url.startswith("file://") else url
     if "://" in src or not os.path.exists(src):
         raise HTTPException(status_code=400, detail="Audio file not found.")
