@@ -539,6 +539,35 @@ int ls_resize_lanczos4_u8(const uint8_t* src, int32_t N, int32_t src_h, int32_t 
 int ls_align_warp_u8(const uint8_t* frames, int32_t N, int32_t H, int32_t W, const double* warp, int32_t out_h,
                      int32_t out_w, int32_t border_value, const void* tables, uint8_t* out, void* stream);
 
+/* ---- video writer, SURVEY.md §8(f) row 3 (additive, ABI stays 14) ------------------ */
+
+/* Motion-JPEG encode of n RGB frames, uint8 [n][H][W][3] contiguous on the device (what
+ * ffmpeg's encoder does for the reference's write_video, util.py:140-160).  Each frame
+ * becomes the entropy-coded scan of one baseline JPEG: 8-bit, YCbCr 4:2:0 (MCU = Y0 Y1 Y2
+ * Y3 Cb Cr), pixels past the right / bottom edge replicating the last column / row, the
+ * Annex K quantisation tables scaled by the libjpeg quality rule (scale = 5000 / q below
+ * 50, 200 - 2 q from 50; entry = clamp((base * scale + 50) / 100, 1, 255)), the Annex K
+ * Huffman tables, a restart interval of ls_mjpeg_restart_interval() MCUs (DC predictors
+ * reset, last byte padded with 1 bits, RSTm between intervals with m = interval index
+ * mod 8, none after the last), 0x00 stuffed after every 0xFF.  Integer arithmetic
+ * throughout (libjpeg's rgb_ycc_convert, h2v2_downsample, jpeg_fdct_islow and
+ * quantiser), so the bytes are reproducible bit for bit.  The
+ * caller adds the headers (SOI .. SOS) and EOI: latentsync_amd.video.jpeg_headers.
+ *   out      uint8 [out_capacity]: the scans, frame after frame
+ *   offsets  int64 [n + 1]: frame f occupies out[offsets[f] .. offsets[f + 1])
+ * Bytes that would land at or past out_capacity are dropped while the offsets stay
+ * exact, so offsets[n] > out_capacity tells the caller to retry with a larger buffer.
+ * Frames are processed in batches of a fixed budget: the workspace
+ * (ls_mjpeg_workspace_bytes) does not grow with n past one batch.  No allocation, no
+ * synchronisation.  LS_ERR_INVALID, nothing launched: null pointers, quality outside
+ * 1..100, n < 1, H or W outside 1..65535, more than 800000 MCUs per frame, negative
+ * out_capacity (ls_mjpeg_workspace_bytes returns 0 for such sizes); LS_ERR_WORKSPACE:
+ * workspace null or too small. */
+int ls_mjpeg_restart_interval(void);
+size_t ls_mjpeg_workspace_bytes(int32_t n, int32_t H, int32_t W);
+int ls_mjpeg_encode(const uint8_t* frames, int32_t n, int32_t H, int32_t W, int32_t quality, uint8_t* out,
+                    int64_t out_capacity, int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream);
+
 int ls_abi_version(void);
 const char* ls_last_error(void);
 

@@ -140,7 +140,11 @@ _SIGS = {
                                         c_vp, C.c_size_t, c_vp]),
     "ls_align_warp_u8": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, C.c_int32, C.c_int32, C.c_int32,
                                    c_vp, c_vp, c_vp]),
-    "ls_add_rows": (C.c_int, [c_vp, C.c_int64, C.c_int32, C.c_int32, c_vp, C.c_int32, c_vp, C.c_int32, c_vp]),
+    "ls_mjpeg_restart_interval": (C.c_int, []),
+    "ls_mjpeg_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "ls_mjpeg_encode": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_vp, C.c_int64, c_vp, c_vp,
+                                  C.c_size_t, c_vp]),
+    "ls_add_rows":(C.c_int, [c_vp, C.c_int64, C.c_int32, C.c_int32, c_vp, C.c_int32, c_vp, C.c_int32, c_vp]),
 }
 
 EXPORTED = tuple(_SIGS)

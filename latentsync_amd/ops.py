@@ -530,6 +530,45 @@ def resample(x, sr_in, sr_out):
     return y
 
 
+def mjpeg_encode(frames_u8, quality=95, workspace=None):
+    """Motion-JPEG scans of uint8 RGB frames (n, H, W, 3) on the device (ls_mjpeg_encode):
+    -> (bytes uint8 (total,), offsets int64 (n + 1,)), both on the device; frame f's
+    entropy-coded scan is bytes[offsets[f]:offsets[f + 1]] (headers: video.jpeg_headers).
+    The output buffer starts at half the raw size and the call is repeated once with the
+    exact size in the rare case the scans are larger (the kernels drop what does not fit
+    and still report exact offsets).  ``workspace``: a caller's uint8 scratch tensor of at
+    least ls_mjpeg_workspace_bytes.  There is no CPU path."""
+    lib = _lib.load()
+    if (not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or
+            frames_u8.shape[-1] != 3 or not frames_u8.is_cuda):
+        raise ValueError("mjpeg_encode: uint8 (n, H, W, 3) on the device expected, got "
+                         f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
+    if not frames_u8.is_contiguous():
+        raise ValueError("mjpeg_encode: frames must be contiguous")
+    n, H, W, _ = frames_u8.shape
+    device = frames_u8.device
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    if n == 0:
+        return torch.empty(0, dtype=torch.uint8, device=device), offsets
+    quality = int(quality)
+    with torch.cuda.device(device):
+        need = lib.ls_mjpeg_workspace_bytes(n, H, W)
+        if workspace is None:
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+        elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != device:
+            raise ValueError("mjpeg_encode: workspace must be a contiguous uint8 tensor on the frames' device")
+        capacity = n * H * W * 3 // 2 + 4096
+        for _ in range(2):
+            out = torch.empty(capacity, dtype=torch.uint8, device=device)
+            check(lib.ls_mjpeg_encode(_p(frames_u8), n, H, W, quality, _p(out), capacity, _p(offsets), _p(workspace),
+                                      workspace.numel(), _stream()), "ls_mjpeg_encode")
+            total = int(offsets[-1].item())
+            if total <= capacity:
+                return out[:total], offsets
+            capacity = total
+    raise RuntimeError("mjpeg_encode: the encoded size changed between two runs on the same frames")
+
+
 def prep_pixels(faces_u8, mask, ld=8, pix=None, masked=None):
     lib = _lib.load()
     F_, _, R, _ = faces_u8.shape

@@ -70,14 +70,23 @@ def load_data_pth(data_path):
     return data
 
 
-def read_video_frames(video_path):
+def read_video_frames(video_path, video_fps=None):
     """Original video frames for restore_video: read_video (util.py:46-100) decodes
     with ffmpeg/cv2, which this build does not carry, so the frames come already
-    decoded -- a uint8 (N,H,W,3) .npy, or an .npz holding ``frames``.  Any other
+    decoded -- a uint8 (N,H,W,3) .npy, or an .npz holding ``frames`` -- or from an
+    ``.avi`` (video.read_avi: Motion-JPEG or uncompressed 24-bit frames).  The reference
+    re-encodes its input to ``video_fps`` first (util.py:52-58); frame-rate conversion is
+    out of scope, so an .avi at another rate than ``video_fps`` is refused.  Any other
     path returns None (no warp-back; the aligned faces are written)."""
     if not video_path or not os.path.exists(video_path):
         return None
-    if video_path.endswith(".npy"):
+    if video_path.endswith(".avi"):
+        from .video import read_avi
+        fr, fps, _, _ = read_avi(video_path)
+        if video_fps is not None and abs(fps - float(video_fps)) > 1e-6 * float(video_fps):
+            raise ValueError(f"{video_path}: {fps:g} frames/s, the call asks for video_fps = {video_fps:g} "
+                             "(frame-rate conversion is out of scope: re-encode the file)")
+    elif video_path.endswith(".npy"):
         fr = np.load(video_path, allow_pickle=False)
     elif video_path.endswith(".npz"):
         with np.load(video_path, allow_pickle=False) as z:
@@ -500,7 +509,11 @@ class LipsyncPipeline:
         uint8 (N,H,W,3) ``.npy`` or an ``.npz`` with a ``frames`` array
         (read_video's output, util.py:46-100).  The synced faces are pasted back into
         those frames on the GPU (restore_video, :577) and the result is written as an
-        .npz of the restored frames (uint8) plus the aligned audio.  ``audio_path`` is
+        .npz of the restored frames (uint8) plus the aligned audio -- or, when
+        ``video_out_path`` ends in ``.avi``, as a playable Motion-JPEG AVI with 16-bit PCM
+        audio, compressed on the device at ``video_quality`` (1..100, default 95) and
+        trimmed by ``padding_duration`` as the reference trims its mux (:599-602);
+        ``video_path`` may be such an ``.avi`` too.  ``audio_path`` is
         any PCM or IEEE-float WAV, at any sample rate and channel count: it is decoded
         on the host and converted to mono at ``audio_sample_rate`` (for the .npz) and at
         16 kHz (for Whisper) on the device, as ffmpeg does for the reference
@@ -533,7 +546,7 @@ class LipsyncPipeline:
         # truncated together with the faces, boxes and matrices below; only rank 0
         # restores and writes, so the other ranks never decode or hold them
         rank0 = shard.world_and_rank()[1] == 0
-        video_frames = None if (kwargs.get("faces_only") or not rank0) else read_video_frames(video_path)
+        video_frames = None if (kwargs.get("faces_only") or not rank0) else read_video_frames(video_path, video_fps)
         R = height or faces.shape[-1]
         self.check_inputs(R, width or R, callback_steps)
         # faces stored at another resolution are resized to R in run_windows, as the
@@ -576,6 +589,20 @@ class LipsyncPipeline:
         if video_frames is not None:
             frames_out = self.restore_video(out, video_frames, boxes, affine_matrices)
         n_out = frames_out.shape[0]
+        if video_out_path.endswith(".avi"):
+            # a playable file: Motion-JPEG encoded on the device + PCM audio (video.py).  An
+            # AVI has no side channel for padding_duration, so the reference's trim of the
+            # muxed file (:599-602) is applied here.
+            from .video import trim_counts, write_video
+            keep_f, keep_a = trim_counts(n_out, video_fps, len(audio_samples), audio_sample_rate, padding_duration,
+                                         bool(start_from_backwards or force_video_length))
+            if keep_f < 1:
+                raise ValueError(f"nothing to write: {n_out} frames at {video_fps} frames/s are all padding "
+                                 f"({padding_duration} s)")
+            write_video(video_out_path, frames_out[:keep_f].contiguous(), video_fps,
+                        np.asarray(audio_samples[:keep_a]), audio_sample_rate,
+                        quality=int(kwargs.get("video_quality", 95)))
+            return None
         audio_keep = int(n_out / video_fps * audio_sample_rate)
         np.savez(video_out_path if video_out_path.endswith(".npz") else video_out_path + ".npz",
                  frames=frames_out.cpu().numpy(), audio=np.asarray(audio_samples[:audio_keep]),

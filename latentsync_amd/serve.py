@@ -47,6 +47,7 @@ class RequestPayload(BaseModel):
     text: Optional[str] = None
     use_darken: Optional[bool] = None
     brightness_factor: Optional[float] = 1
+    output_format: Optional[str] = None  # this build: "npz" (default) or "avi" (run_job)
 
 
 def calculate_inverse_factor(original_factor):
@@ -94,10 +95,15 @@ def run_job(pipeline, payload: dict, data_dir: str, results_dir: str, resolution
     if not os.path.exists(audio_path):
         fetch_audio(payload["audio_url"], audio_path)
     os.makedirs(results_dir, exist_ok=True)
-    video_out_path = os.path.join(results_dir, f"{payload['id']}.npz")  # this build's writer (pipeline.py)
+    # this build's writers (pipeline.py): "npz" (raw frames + audio, the default) or "avi"
+    # (Motion-JPEG + PCM, a playable file), chosen by the job's output_format
+    fmt = payload.get("output_format") or "npz"
+    if fmt not in ("npz", "avi"):
+        raise ValueError(f"output_format must be 'npz' or 'avi', got {fmt!r}")
+    video_out_path = os.path.join(results_dir, f"{payload['id']}.{fmt}")
     kw = {} if weight_dtype is None else dict(weight_dtype=weight_dtype)
     pipeline(video_path=video_path, audio_path=audio_path, video_out_path=video_out_path,
-             video_mask_path=video_out_path.replace(".npz", "_mask.npz"), num_frames=16, num_inference_steps=20,
+             video_mask_path=os.path.join(results_dir, f"{payload['id']}_mask.npz"), num_frames=16, num_inference_steps=20,
              guidance_scale=1.5, width=resolution, height=resolution, data_path=data_path,
              start_from_backwards=payload.get("start_from_backwards") or False,
              force_video_length=payload.get("force_video_length") or False,
