@@ -568,6 +568,45 @@ size_t ls_mjpeg_workspace_bytes(int32_t n, int32_t H, int32_t W);
 int ls_mjpeg_encode(const uint8_t* frames, int32_t n, int32_t H, int32_t W, int32_t quality, uint8_t* out,
                     int64_t out_capacity, int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- video reader, SURVEY.md §8(f) (additive, ABI stays 14) ------------------------- */
+
+/* Motion-JPEG decode of n frames of one size into uint8 RGB [n][H][W][3] on the device:
+ * the inverse of ls_mjpeg_encode for any 8-bit baseline JPEG with one interleaved scan
+ * that is greyscale or YCbCr with chroma 1x1 and luma 1x1, 2x1 or 2x2.  The host parses
+ * the segments in front of each scan (latentsync_amd.video.parse_jpeg); the device does
+ * the rest, in libjpeg's integer arithmetic (jdhuff.c, jidctint.c jpeg_idct_islow with a
+ * saturating range limit, jdsample.c fancy upsampling, jdcolor.c),
+ * so the pixels equal libjpeg's bit for bit.
+ *   data     uint8 [data_bytes]: the entropy-coded scans (anything may lie between them)
+ *   frames   int64 [n][8] per frame: [0] first byte of its scan in data, [1] bytes from
+ *            there to the end of its chunk (decoding stops after the last MCU, so an EOI or
+ *            padding behind it is harmless), [2] restart interval in MCUs (0 = none),
+ *            [3] sampling: 0 grey, 1 4:4:4, 2 4:2:2 (luma 2x1), 3 4:2:0 (luma 2x2),
+ *            [4] quantiser index of component c in bits 16c..16c+15, [5] its DC and [6] its
+ *            AC Huffman table index likewise, [7] 0
+ *   quant    uint16 [n_quant][64]: quantiser steps in natural (row-major) order
+ *   huff     int32 [n_huff][228]: per table, jdhuff.c's derived form -- uint16 [256]
+ *            lookahead (length << 8 | symbol for every code of up to 8 bits, else 0),
+ *            int32 [18] maxcode (by length; -1 = no code), int32 [18] valoffset, uint8 [256]
+ *            huffval (video.huff_device_table builds it)
+ *   max_segments  the largest number of restart segments of any frame (sizes the grid
+ *            only: a smaller value is slower, never wrong)
+ *   status   int32 [n]: 0, or why the frame could not be decoded -- 1 descriptor outside
+ *            data, 2 RSTm markers missing, surplus or out of order, 3 a code longer than 16
+ *            bits, 4 a coefficient index past 63, 5 a segment ran out before its MCUs.  The
+ *            other frames of the call are unaffected; a refused frame's pixels are undefined.
+ * No stream content makes the kernels read or write outside their buffers: every byte
+ * index is checked against the segment's end and bytes past it are zero bits.  Frames are
+ * processed in batches of a fixed budget: the workspace (ls_mjpeg_decode_workspace_bytes)
+ * does not grow with n past one batch.  No allocation, no synchronisation.
+ * LS_ERR_INVALID, nothing launched: null pointers, n < 1, H or W outside 3..65535,
+ * negative data_bytes, table counts outside 1..65535 (ls_mjpeg_decode_workspace_bytes
+ * returns 0 for such sizes); LS_ERR_WORKSPACE: workspace null or too small. */
+size_t ls_mjpeg_decode_workspace_bytes(int32_t n, int32_t H, int32_t W);
+int ls_mjpeg_decode(const uint8_t* data, int64_t data_bytes, const int64_t* frames, int32_t n, int32_t H, int32_t W,
+                    const uint16_t* quant, int32_t n_quant, const int32_t* huff, int32_t n_huff, int32_t max_segments,
+                    uint8_t* out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 int ls_abi_version(void);
 const char* ls_last_error(void);
 

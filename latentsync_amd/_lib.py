@@ -144,6 +144,9 @@ _SIGS = {
     "ls_mjpeg_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "ls_mjpeg_encode": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_vp, C.c_int64, c_vp, c_vp,
                                   C.c_size_t, c_vp]),
+    "ls_mjpeg_decode_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "ls_mjpeg_decode": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, C.c_int32, c_vp,
+                                  C.c_int32, C.c_int32, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
     "ls_add_rows":(C.c_int, [c_vp, C.c_int64, C.c_int32, C.c_int32, c_vp, C.c_int32, c_vp, C.c_int32, c_vp]),
 }
 

@@ -569,6 +569,43 @@ def mjpeg_encode(frames_u8, quality=95, workspace=None):
     raise RuntimeError("mjpeg_encode: the encoded size changed between two runs on the same frames")
 
 
+def mjpeg_decode(data, frames, H, W, quant, huff, max_segments=1, workspace=None):
+    """Motion-JPEG scans on the device -> (RGB uint8 (n, H, W, 3), status int32 (n,)), both
+    on the device (ls_mjpeg_decode).  ``data``: uint8 1-D, the entropy-coded scans;
+    ``frames``: int64 (n, 8) descriptors; ``quant``: uint16 / int16 (n_quant, 64);
+    ``huff``: int32 (n_huff, 228) -- the layouts are in include/ls_hip.h,
+    video.decode_frames builds them.  A non-zero status marks a frame that could not be
+    decoded; the others are exact.  ``workspace``: a caller's uint8 scratch tensor of at
+    least ls_mjpeg_decode_workspace_bytes.  There is no CPU path."""
+    lib = _lib.load()
+    if not torch.cuda.is_available():
+        raise RuntimeError("mjpeg_decode: the Motion-JPEG decoder runs on the HIP device, and none is present")
+    for name, t, dt, tail in (("data", data, (torch.uint8,), None), ("frames", frames, (torch.int64,), 8),
+                              ("quant", quant, (torch.uint16, torch.int16), 64), ("huff", huff, (torch.int32,), 228)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in dt or not t.is_contiguous() or \
+                t.dim() != (1 if tail is None else 2) or (tail is not None and (t.shape[1] != tail or t.shape[0] < 1)):
+            raise ValueError(f"mjpeg_decode: {name} must be a contiguous device tensor of {dt[0]}"
+                             + ("" if tail is None else f" (rows, {tail})") + ", got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    device = data.device
+    if any(t.device != device for t in (frames, quant, huff)):
+        raise ValueError("mjpeg_decode: data, frames, quant and huff must be on one device")
+    n, H, W = frames.shape[0], int(H), int(W)
+    with torch.cuda.device(device):
+        need = lib.ls_mjpeg_decode_workspace_bytes(n, H, W)
+        if workspace is None:
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+        elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != device:
+            raise ValueError("mjpeg_decode: workspace must be a contiguous uint8 tensor on the data's device")
+        ok = need > 0  # 0: a size ls_mjpeg_decode refuses; allocate nothing of that size
+        out = torch.empty((n, H, W, 3) if ok else (0,), dtype=torch.uint8, device=device)
+        status = torch.empty(n, dtype=torch.int32, device=device)
+        check(lib.ls_mjpeg_decode(_p(data), data.numel(), _p(frames), n, H, W, _p(quant), quant.shape[0], _p(huff),
+                                  huff.shape[0], int(max_segments), _p(out if ok else status), _p(status),
+                                  _p(workspace), workspace.numel(), _stream()), "ls_mjpeg_decode")
+    return out, status
+
+
 def prep_pixels(faces_u8, mask, ld=8, pix=None, masked=None):
     lib = _lib.load()
     F_, _, R, _ = faces_u8.shape

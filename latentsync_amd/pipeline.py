@@ -70,19 +70,22 @@ def load_data_pth(data_path):
     return data
 
 
-def read_video_frames(video_path, video_fps=None):
+def read_video_frames(video_path, video_fps=None, device=None):
     """Original video frames for restore_video: read_video (util.py:46-100) decodes
     with ffmpeg/cv2, which this build does not carry, so the frames come already
     decoded -- a uint8 (N,H,W,3) .npy, or an .npz holding ``frames`` -- or from an
-    ``.avi`` (video.read_avi: Motion-JPEG or uncompressed 24-bit frames).  The reference
+    ``.avi`` (Motion-JPEG or uncompressed 24-bit frames).  With a HIP ``device`` and every
+    frame in the device subset of JPEG the .avi is decoded there and a device tensor comes
+    back (video.read_avi_device: only compressed bytes are uploaded); otherwise, and on
+    CPU-only hosts, it is video.read_avi's host decode, as a numpy array.  The reference
     re-encodes its input to ``video_fps`` first (util.py:52-58); frame-rate conversion is
     out of scope, so an .avi at another rate than ``video_fps`` is refused.  Any other
     path returns None (no warp-back; the aligned faces are written)."""
     if not video_path or not os.path.exists(video_path):
         return None
     if video_path.endswith(".avi"):
-        from .video import read_avi
-        fr, fps, _, _ = read_avi(video_path)
+        from .video import read_avi_auto
+        fr, fps, _, _ = read_avi_auto(video_path, device)
         if video_fps is not None and abs(fps - float(video_fps)) > 1e-6 * float(video_fps):
             raise ValueError(f"{video_path}: {fps:g} frames/s, the call asks for video_fps = {video_fps:g} "
                              "(frame-rate conversion is out of scope: re-encode the file)")
@@ -93,7 +96,7 @@ def read_video_frames(video_path, video_fps=None):
             fr = z["frames"]
     else:
         return None
-    if fr.dtype != np.uint8 or fr.ndim != 4 or fr.shape[-1] != 3:
+    if fr.dtype != (torch.uint8 if torch.is_tensor(fr) else np.uint8) or fr.ndim != 4 or fr.shape[-1] != 3:
         raise ValueError(f"{video_path}: expected uint8 frames (N,H,W,3), got {fr.dtype} {fr.shape}")
     return fr
 
@@ -546,7 +549,9 @@ class LipsyncPipeline:
         # truncated together with the faces, boxes and matrices below; only rank 0
         # restores and writes, so the other ranks never decode or hold them
         rank0 = shard.world_and_rank()[1] == 0
-        video_frames = None if (kwargs.get("faces_only") or not rank0) else read_video_frames(video_path, video_fps)
+        video_frames = None
+        if rank0 and not kwargs.get("faces_only"):
+            video_frames = read_video_frames(video_path, video_fps, self.device)
         R = height or faces.shape[-1]
         self.check_inputs(R, width or R, callback_steps)
         # faces stored at another resolution are resized to R in run_windows, as the

@@ -5,10 +5,13 @@ its audio mux (lipsync_pipeline.py:596-603), for the one format that needs no th
 codec.  The frames are compressed where they already are: ops.mjpeg_encode (ls_mjpeg_encode,
 csrc/ls_video.hip) returns every frame's entropy-coded scan, ``jpeg_headers`` builds the
 segments in front of it on the host, and ``write_avi`` muxes complete JPEG byte strings
-with the audio.  ``read_avi`` is the way back in for ``read_video_frames``: MJPG frames
-(decoded with Pillow -- JPEG entropy decoding is serial host work, what ffmpeg does for
-the reference) and uncompressed 24-bit BI_RGB frames.  H.264 / mp4, OpenDML files above
-2 GiB and frame-rate conversion are out of scope.
+with the audio.  The way back in for ``read_video_frames`` is ``read_avi_device``: the host
+reads each MJPG frame's headers (``parse_jpeg``), the device decodes the scans
+(ops.mjpeg_decode, ls_mjpeg_decode, csrc/ls_video_dec.hip), so only compressed bytes are
+uploaded; uncompressed 24-bit BI_RGB frames are uploaded as stored.  ``read_avi`` is the same
+reader with the frames decoded on the host (MJPG with Pillow), for CPU-only hosts and for
+JPEG flavours outside the device subset.  H.264 / mp4, OpenDML files above 2 GiB and
+frame-rate conversion are out of scope.
 """
 import io
 import struct
@@ -107,6 +110,274 @@ def encode_frames(frames_dev_u8, quality=95):
     off = offsets.cpu().tolist()
     raw = data.cpu().numpy().tobytes()
     return [head + raw[off[i]:off[i + 1]] + JPEG_EOI for i in range(n)]
+
+
+# ---------------------------------------------------------------------------- JPEG reader
+
+SAMPLING_MODES = {(1, 1): 1, (2, 1): 2, (2, 2): 3}  # luma (h, v) with chroma 1x1 -> the device's sampling mode
+MODE_NAMES = ("grey", "4:4:4", "4:2:2", "4:2:0")
+_SOF_NAMES = {0xC1: "extended sequential (SOF1)", 0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)",
+              0xC9: "arithmetic coding (SOF9)", 0xCA: "arithmetic coding (SOF10)", 0xCB: "arithmetic coding (SOF11)"}
+_STD_HUFF = {(0, 0): HUFF_DC_LUMA, (0, 1): HUFF_DC_CHROMA, (1, 0): HUFF_AC_LUMA, (1, 1): HUFF_AC_CHROMA}
+
+
+class JpegInfo:
+    """What ``parse_jpeg`` found in front of a frame's scan.  ``reason`` is None when the
+    frame is in the device subset (ls_mjpeg_decode), else why it is not; the geometry and
+    table fields are complete only in the first case.
+      H, W, ncomp; mode (index into MODE_NAMES); Ri (MCUs per restart interval, 0 = none);
+      quant[c]: 64 quantiser steps of component c in natural order;
+      huff_dc[c], huff_ac[c]: (BITS, HUFFVAL) of component c;
+      scan_start: index in the byte string of the first entropy-coded byte (the scan runs
+      to the end of the string); n_mcu, n_segments."""
+
+    def __init__(self):
+        self.H = self.W = self.ncomp = self.mode = self.Ri = self.scan_start = self.n_mcu = self.n_segments = 0
+        self.quant, self.huff_dc, self.huff_ac, self.reason = [], [], [], None
+
+    @property
+    def on_device(self):
+        return self.reason is None
+
+
+def parse_jpeg(jpg):
+    """Read the segments in front of the scan of one JPEG byte string -> JpegInfo.  SOI,
+    APPn / COM (skipped; an Adobe APP14 is read for its transform), DQT, SOF, DHT, DRI and
+    SOS are handled.  A frame without DHT gets the Annex K tables, the MJPG-in-AVI
+    convention.  Anything outside the device subset -- 8-bit baseline (SOF0), one scan with
+    Ss = 0, Se = 63, Ah = Al = 0, W and H >= 3, one component or Y 1x1 / 2x1 / 2x2 with Cb
+    and Cr 1x1 -- sets ``reason``; a truncated or malformed header is a ValueError."""
+    jpg = bytes(jpg)
+    info = JpegInfo()
+    n = len(jpg)
+    if n < 4 or jpg[:2] != b"\xff\xd8":
+        raise ValueError("not a JPEG: no SOI marker")
+    qt, q16, huff, comps, reasons = {}, set(), {}, None, []
+    adobe = None
+    i = 2
+    while True:
+        if i + 2 > n:
+            raise ValueError(f"truncated JPEG header: no SOS marker in {n} bytes")
+        if jpg[i] != 0xFF:
+            raise ValueError(f"malformed JPEG header: byte 0x{jpg[i]:02X} at {i} where a marker is expected")
+        m = jpg[i + 1]
+        if m == 0xFF:  # fill byte
+            i += 1
+            continue
+        if m == 0x01 or 0xD0 <= m <= 0xD7:  # stand-alone markers
+            i += 2
+            continue
+        if m == 0xD9:
+            raise ValueError("malformed JPEG: EOI before any scan")
+        if i + 4 > n:
+            raise ValueError(f"truncated JPEG header: marker 0x{m:02X} at byte {i} has no length")
+        ln = struct.unpack(">H", jpg[i + 2:i + 4])[0]
+        if ln < 2 or i + 2 + ln > n:
+            raise ValueError(f"truncated JPEG header: segment 0x{m:02X} at byte {i} declares {ln} bytes, "
+                             f"{n - i - 2} are left")
+        p = jpg[i + 4:i + 2 + ln]
+        if m == 0xDB:
+            k = 0
+            while k < len(p):
+                pq, tq = p[k] >> 4, p[k] & 15
+                size = 128 if pq else 64
+                if pq > 1 or k + 1 + size > len(p):
+                    raise ValueError("malformed JPEG: bad DQT segment")
+                if pq:
+                    q16.add(tq)
+                    zz = struct.unpack(">64H", p[k + 1:k + 129])
+                else:
+                    q16.discard(tq)
+                    zz = p[k + 1:k + 65]
+                nat = [0] * 64
+                for z, v in enumerate(zz):
+                    nat[ZIGZAG[z]] = int(v)
+                qt[tq] = tuple(nat)
+                k += 1 + size
+        elif m == 0xC4:
+            k = 0
+            while k < len(p):
+                if k + 17 > len(p):
+                    raise ValueError("malformed JPEG: bad DHT segment")
+                tc, th = p[k] >> 4, p[k] & 15
+                bits = tuple(p[k + 1:k + 17])
+                cnt = sum(bits)
+                if tc > 1 or cnt > 256 or k + 17 + cnt > len(p):
+                    raise ValueError("malformed JPEG: bad DHT segment")
+                huff[(tc, th)] = (bits, tuple(p[k + 17:k + 17 + cnt]))
+                k += 17 + cnt
+        elif m == 0xCC:
+            reasons.append("arithmetic coding (DAC)")
+        elif 0xC0 <= m <= 0xCF and m != 0xC8:
+            if comps is not None:
+                raise ValueError("malformed JPEG: two SOF segments")
+            if len(p) < 6 or len(p) < 6 + 3 * p[5]:
+                raise ValueError("truncated JPEG header: short SOF segment")
+            if m != 0xC0:
+                reasons.append(_SOF_NAMES.get(m, f"SOF{m - 0xC0}"))
+            prec, info.H, info.W, info.ncomp = struct.unpack(">BHHB", p[:6])
+            if prec != 8:
+                reasons.append(f"{prec}-bit samples")
+            comps = [(p[6 + 3 * c], p[7 + 3 * c] >> 4, p[7 + 3 * c] & 15, p[8 + 3 * c]) for c in range(info.ncomp)]
+        elif m == 0xDD:
+            if len(p) < 2:
+                raise ValueError("truncated JPEG header: short DRI segment")
+            info.Ri = struct.unpack(">H", p[:2])[0]
+        elif m == 0xEE and p[:5] == b"Adobe" and len(p) >= 12:
+            adobe = p[11]
+        elif m == 0xDA:
+            if comps is None:
+                raise ValueError("malformed JPEG: SOS before SOF")
+            if len(p) < 1 or len(p) < 4 + 2 * p[0]:
+                raise ValueError("truncated JPEG header: short SOS segment")
+            ns = p[0]
+            scan = [(p[1 + 2 * c], p[2 + 2 * c] >> 4, p[2 + 2 * c] & 15) for c in range(ns)]
+            ss, se, ahal = p[1 + 2 * ns:4 + 2 * ns]
+            info.scan_start = i + 2 + ln
+            break
+        i += 2 + ln
+    if info.ncomp not in (1, 3):
+        reasons.append(f"{info.ncomp} components")
+    if ns != info.ncomp or [s[0] for s in scan] != [c[0] for c in comps]:
+        reasons.append("more than one scan")
+    elif (ss, se, ahal) != (0, 63, 0):
+        reasons.append(f"scan parameters Ss = {ss}, Se = {se}, Ah/Al = 0x{ahal:02X}")
+    if info.H < 3 or info.W < 3:
+        reasons.append(f"{info.W}x{info.H} is smaller than 3x3")
+    if info.ncomp == 3:
+        if adobe == 0 or (adobe is None and [c[0] for c in comps] == [82, 71, 66]):
+            reasons.append("RGB components (Adobe transform 0)")
+        fac = [(c[1], c[2]) for c in comps]
+        if fac[1] != (1, 1) or fac[2] != (1, 1) or fac[0] not in SAMPLING_MODES:
+            reasons.append("sampling factors " + ", ".join(f"{h}x{v}" for h, v in fac))
+        else:
+            info.mode = SAMPLING_MODES[fac[0]]
+    if any(c[3] in q16 for c in comps):
+        reasons.append("16-bit quantisation tables")
+    if reasons:
+        info.reason = "; ".join(reasons)
+        return info
+    for (_, _, _, tq), (_, td, ta) in zip(comps, scan):
+        if tq not in qt:
+            raise ValueError(f"malformed JPEG: quantisation table {tq} is not defined")
+        info.quant.append(qt[tq])
+        for tc, th, dst in ((0, td, info.huff_dc), (1, ta, info.huff_ac)):
+            tab = huff.get((tc, th)) if huff else _STD_HUFF.get((tc, th))
+            if tab is None:
+                raise ValueError(f"malformed JPEG: Huffman table {'DA'[tc]}C {th} is not defined")
+            if tc == 0 and any(v > 15 for v in tab[1]):
+                raise ValueError("malformed JPEG: a DC Huffman table holds a category above 15")
+            dst.append(tab)
+    hs, vs = (1, 1) if info.mode == 0 else next(k for k, v in SAMPLING_MODES.items() if v == info.mode)
+    info.n_mcu = -(-info.W // (8 * hs)) * -(-info.H // (8 * vs))
+    info.n_segments = -(-info.n_mcu // info.Ri) if 0 < info.Ri < info.n_mcu else 1
+    return info
+
+
+HUFF_TABLE_INTS = 228  # int32 per device Huffman table (include/ls_hip.h)
+
+
+def huff_device_table(bits, vals):
+    """(BITS, HUFFVAL) -> int32 (228,), jdhuff.c's derived table (jpeg_make_d_derived_tbl):
+    uint16 [256] lookahead, length << 8 | symbol for every code of up to 8 bits; int32 [18]
+    maxcode by length (-1 = no code of that length, [17] a sentinel); int32 [18] valoffset;
+    uint8 [256] HUFFVAL."""
+    sizes = np.repeat(np.arange(1, 17), bits)
+    if len(sizes) != len(vals) or len(sizes) > 256:
+        raise ValueError("malformed JPEG: Huffman table counts and values disagree")
+    codes = np.zeros(len(sizes), np.int64)
+    code = 0
+    for k in range(len(sizes)):
+        if k and sizes[k] != sizes[k - 1]:
+            code <<= int(sizes[k] - sizes[k - 1])
+        if code >= 1 << int(sizes[k]):
+            raise ValueError("malformed JPEG: Huffman table has more codes than its lengths allow")
+        codes[k] = code
+        code += 1
+    look = np.zeros(256, np.uint16)
+    maxcode = np.full(18, -1, np.int32)
+    valoff = np.zeros(18, np.int32)
+    maxcode[17] = 0xFFFFF
+    p = 0
+    for l in range(1, 17):
+        if bits[l - 1]:
+            valoff[l] = p - codes[p]
+            p += bits[l - 1]
+            maxcode[l] = codes[p - 1]
+    for k in np.nonzero(sizes <= 8)[0]:
+        l = int(sizes[k])
+        first = int(codes[k]) << (8 - l)
+        look[first:first + (1 << (8 - l))] = (l << 8) | int(vals[k])
+    val = np.zeros(256, np.uint8)
+    val[:len(vals)] = vals
+    return np.concatenate([look.view(np.int32), maxcode, valoff, val.view(np.int32)])
+
+
+_STATUS_TEXT = {1: "the scan lies outside the buffer", 2: "restart markers missing, surplus or out of order",
+                3: "a Huffman code longer than 16 bits", 4: "a coefficient index past 63",
+                5: "the entropy-coded data ends before the last MCU"}
+
+
+def pack_frames(jpegs):
+    """The host half of ``decode_frames``: n JPEG byte strings (or (bytes, JpegInfo) pairs)
+    of one size -> (scans bytes, descriptors int64 (n, 8), quantisers int16 (n_quant, 64),
+    Huffman tables int32 (n_huff, 228), max segments per frame, H, W), the arguments of
+    ops.mjpeg_decode in the layouts of include/ls_hip.h.  The scans are concatenated and
+    the tables deduplicated: most files repeat one set, files with optimised tables
+    carry one per frame."""
+    infos = [j if isinstance(j, tuple) else (bytes(j), parse_jpeg(j)) for j in jpegs]
+    if not infos:
+        raise ValueError("decode_frames: no frames")
+    H, W = infos[0][1].H, infos[0][1].W
+    qidx, hidx, desc, scans, pos = {}, {}, [], [], 0
+    pack = lambda idx: sum(v << (16 * c) for c, v in enumerate(idx))
+    for i, (jpg, info) in enumerate(infos):
+        if not info.on_device:
+            raise ValueError(f"frame {i} is not in the device subset of JPEG ({info.reason})")
+        if (info.H, info.W) != (H, W):
+            raise ValueError(f"frame {i} is {info.W}x{info.H}, frame 0 is {W}x{H}")
+        q = [qidx.setdefault(t, len(qidx)) for t in info.quant]
+        dc = [hidx.setdefault(t, len(hidx)) for t in info.huff_dc]
+        ac = [hidx.setdefault(t, len(hidx)) for t in info.huff_ac]
+        scan = jpg[info.scan_start:]
+        desc.append((pos, len(scan), info.Ri, info.mode, pack(q), pack(dc), pack(ac), 0))
+        scans.append(scan)
+        pos += len(scan)
+    if len(qidx) > 65535 or len(hidx) > 65535:
+        raise ValueError("decode_frames: more than 65535 distinct tables in one call")
+    quant = np.array(list(qidx), np.int16)  # steps are 1..255
+    huff = np.stack([huff_device_table(*t) for t in hidx])
+    return (b"".join(scans), np.array(desc, np.int64), quant, huff, max(info.n_segments for _, info in infos), H, W)
+
+
+def decode_frames_status(jpegs, device):
+    """``decode_frames`` without the final check: -> (frames uint8 (n, H, W, 3) on the
+    device, status list of n ints).  Frames with a non-zero status are undefined, the
+    others exact."""
+    import torch
+    from . import ops
+    scans, desc, quant, huff, max_seg, H, W = pack_frames(jpegs)
+    if not torch.cuda.is_available():
+        raise RuntimeError("decode_frames: the Motion-JPEG decoder runs on the HIP device, and none is present "
+                           "(read_avi decodes on the host)")
+    device = torch.device(device)
+    up = lambda a: torch.from_numpy(a).to(device)
+    data = up(np.frombuffer(scans or b"\0", np.uint8).copy())
+    frames, status = ops.mjpeg_decode(data, up(desc), H, W, up(quant), up(huff), max_seg)
+    return frames, status.cpu().tolist()
+
+
+def decode_frames(jpegs, device):
+    """n complete JPEG byte strings of one size -> uint8 (n, H, W, 3) RGB on ``device``
+    (ls_mjpeg_decode).  The host reads the headers, deduplicates the quantisers and the
+    Huffman tables and uploads the concatenated scans; everything else runs on the device.
+    A frame outside the device subset or one the device could not decode is a ValueError
+    naming it."""
+    frames, status = decode_frames_status(jpegs, device)
+    for i, s in enumerate(status):
+        if s:
+            raise ValueError(f"frame {i} is not a decodable JPEG ({_STATUS_TEXT.get(s, f'status {s}')})")
+    return frames
 
 
 # ---------------------------------------------------------------------------- AVI writer
@@ -274,12 +545,12 @@ def _decode_bi_rgb(raw, W, H, path):
     return np.ascontiguousarray(a if top_down else a[::-1])
 
 
-def read_avi(path):
-    """-> (frames uint8 (N, H, W, 3) RGB, fps, audio float32 mono or None, sample_rate).
-    Walks the RIFF tree (unknown chunks skipped, pad bytes honoured, 'rec ' lists
-    descended); MJPG frames are decoded with Pillow, 24-bit BI_RGB frames directly; PCM
-    16-bit audio is returned as s16 / 32768 (more channels are averaged).  Any other video
-    codec, audio format, or a truncated file is a ValueError naming the file."""
+def _walk_avi(path):
+    """The RIFF walk shared by read_avi and read_avi_device: -> (codec 'mjpg' | 'rgb', W,
+    signed H, fps, list of video chunk payloads, audio float32 mono or None, sample_rate).
+    Unknown chunks are skipped, pad bytes honoured, 'rec ' lists descended; PCM 16-bit
+    audio is returned as s16 / 32768 (more channels are averaged).  Any other video codec,
+    audio format, or a truncated file is a ValueError naming the file."""
     with open(path, "rb") as f:
         buf = f.read()
     if len(buf) < 12 or buf[:4] != b"RIFF" or buf[8:12] != b"AVI ":
@@ -351,6 +622,20 @@ def read_avi(path):
                 pcm.append(buf[p:p + size])
 
     walk(*movi)
+    audio = None
+    if aud is not None:
+        a = np.frombuffer(b"".join(pcm), "<i2")
+        a = a[:len(a) // n_ch * n_ch].astype(np.float32) / np.float32(32768.0)
+        audio = a if n_ch == 1 else a.reshape(-1, n_ch).mean(axis=1, dtype=np.float32)
+    return codec, W, Hs, fps, frames, audio, sr
+
+
+def read_avi(path):
+    """-> (frames uint8 (N, H, W, 3) RGB, fps, audio float32 mono or None, sample_rate),
+    all on the host: MJPG frames are decoded with Pillow, 24-bit BI_RGB frames directly
+    (the route of CPU-only hosts; ``read_avi_device`` decodes on the device).  The
+    container rules and errors are ``_walk_avi``'s."""
+    codec, W, Hs, fps, frames, audio, sr = _walk_avi(path)
     if codec == "mjpg":
         from PIL import Image
         dec = []
@@ -366,9 +651,65 @@ def read_avi(path):
     else:
         dec = [_decode_bi_rgb(j, W, Hs, path) for j in frames]
     out = np.stack(dec) if dec else np.zeros((0, abs(Hs), W, 3), np.uint8)
-    audio = None
-    if aud is not None:
-        a = np.frombuffer(b"".join(pcm), "<i2")
-        a = a[:len(a) // n_ch * n_ch].astype(np.float32) / np.float32(32768.0)
-        audio = a if n_ch == 1 else a.reshape(-1, n_ch).mean(axis=1, dtype=np.float32)
     return out, fps, audio, sr
+
+
+def _avi_device_infos(frames):
+    """parse_jpeg of every MJPG chunk -> (list of JpegInfo, None), or (None, why) when a
+    header cannot be parsed or a frame is outside the device subset."""
+    infos = []
+    for i, j in enumerate(frames):
+        try:
+            info = parse_jpeg(j)
+        except ValueError as e:
+            return None, f"frame {i}: {e}"
+        if not info.on_device:
+            return None, f"frame {i}: {info.reason}"
+        infos.append(info)
+    return infos, None
+
+
+def read_avi_device(path, device, _walked=None):
+    """``read_avi`` with the frames decoded on ``device``: -> (frames uint8 (N, H, W, 3) RGB
+    device tensor, fps, audio, sample_rate).  MJPG frames go through ``decode_frames`` (only
+    compressed bytes are uploaded); BI_RGB frames are uploaded as stored and flipped there.
+    Errors are read_avi's, plus a ValueError for a frame outside the device subset of JPEG
+    (read_avi decodes those on the host)."""
+    import torch
+    codec, W, Hs, fps, frames, audio, sr = _walked or _walk_avi(path)
+    device = torch.device(device)
+    H = abs(Hs)
+    if not frames:
+        return torch.zeros((0, H, W, 3), dtype=torch.uint8, device=device), fps, audio, sr
+    if codec == "mjpg":
+        infos, why = _avi_device_infos(frames)
+        if infos is None:
+            raise ValueError(f"{path}: {why} -- not in the device subset of JPEG")
+        for i, info in enumerate(infos):
+            if (info.H, info.W) != (H, W):
+                raise ValueError(f"{path}: frame {i} is {info.W}x{info.H}, the header says {W}x{H}")
+        out, status = decode_frames_status(list(zip(frames, infos)), device)
+        for i, s in enumerate(status):
+            if s:
+                raise ValueError(f"{path}: frame {i} is not a decodable JPEG ({_STATUS_TEXT.get(s, f'status {s}')})")
+    else:
+        stride = (W * 3 + 3) & ~3
+        for j in frames:
+            if len(j) < stride * H:
+                raise ValueError(f"{path}: truncated BI_RGB frame ({len(j)} bytes, {stride * H} expected)")
+        raw = torch.frombuffer(bytearray(b"".join(j[:stride * H] for j in frames)), dtype=torch.uint8).to(device)
+        out = raw.view(len(frames), H, stride)[:, :, :W * 3].reshape(len(frames), H, W, 3).flip(3)  # BGR -> RGB
+        out = (out if Hs < 0 else out.flip(1)).contiguous()  # bottom-up unless the height is negative
+    return out, fps, audio, sr
+
+
+def read_avi_auto(path, device=None):
+    """The reader of pipeline.read_video_frames: ``read_avi_device`` when ``device`` is a
+    HIP device and every frame is in the device subset, else ``read_avi``, unchanged."""
+    import torch
+    if device is None or not torch.cuda.is_available() or torch.device(device).type != "cuda":
+        return read_avi(path)
+    walked = _walk_avi(path)
+    if walked[0] == "mjpg" and _avi_device_infos(walked[4])[0] is None:
+        return read_avi(path)
+    return read_avi_device(path, device, walked)
