@@ -607,6 +607,44 @@ int ls_mjpeg_decode(const uint8_t* data, int64_t data_bytes, const int64_t* fram
                     const uint16_t* quant, int32_t n_quant, const int32_t* huff, int32_t n_huff, int32_t max_segments,
                     uint8_t* out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- face brightness restore of use_darken requests (additive, ABI stays 14) --------- */
+
+/* What the reference's write_video does to every output frame when `use_darken and
+ * brightness_factor` (darken_restore.enhance_face_brightness, util.py:150-151), in place
+ * on n RGB frames, uint8 [n][H][W][3] contiguous on the device.  DESIGN.md section 4.4 is
+ * the definition: per detected frame a mask (two convex hulls filled, a dilate x dilate
+ * box maximum with anchor dilate / 2, an n_taps Gaussian with BORDER_REFLECT_101, taps
+ * added in index order with every product and sum rounded to float32), smoothed over
+ * time (0.7 last + 0.3 mask; decaying by 0.8 over frames without a face), then every pixel
+ * of a processed frame through OpenCV's 8-bit RGB -> HSV (hue range 180) -> RGB with
+ * V' = clip(V (1 + g), 0, max_value) when `brighten`, else clip(V (1 - g), 0, 255), g = mask c.
+ * The host half (latentsync_amd.darken) builds the tables:
+ *   plan     int32 [n][4] on the device, per frame: [0] mode -- 0 leave the frame bit-identical,
+ *            1 a detected frame with no mask before it, 2 a detected frame blended with the
+ *            last mask, 3 no face: the last mask, which then decays, 4 no face and no mask yet:
+ *            0.8 x the mask of frame `first_valid`; [1] its first vertex in verts, [2] the
+ *            vertex count of hull A, [3] of hull B, which follows A (modes 1 and 2 only)
+ *   verts    int32 [n_verts][2] on the device: hull vertices (x, y) in pixels, each hull
+ *            strictly convex and ordered so that (b - a) x (p - a) >= 0 for consecutive
+ *            vertices a, b and every inside point p; one or two vertices make a point or a
+ *            segment.  A plan row that points outside verts gives an empty mask.
+ *   first_valid  the frame (mode 1 or 2) whose mask serves mode 4, or -1
+ *   roi_*    the region of interest: it holds every hull pixel inside the frame, grown by
+ *            dilate + n_taps / 2; outside it the mask is exactly zero and is not computed
+ *   taps     float [n_taps] on the device
+ * Frames are processed in batches of frames_per_batch (0: a fixed budget); the workspace
+ * (ls_face_brighten_workspace_bytes, 0 for sizes it refuses) holds the planes of one batch
+ * plus the state carried across batches and does not grow with n.  No allocation, no
+ * synchronisation.  LS_ERR_INVALID, nothing launched: null pointers, n < 1, H or W outside
+ * 1..65535, n_taps even, below 1 or above 129, dilate < 1, max_value outside 0..255,
+ * first_valid outside -1..n-1, a region of interest that is empty or not inside the frame;
+ * LS_ERR_WORKSPACE: workspace null or too small. */
+size_t ls_face_brighten_workspace_bytes(int32_t n, int32_t roi_h, int32_t roi_w, int32_t frames_per_batch);
+int ls_face_brighten(uint8_t* frames, int32_t n, int32_t H, int32_t W, const int32_t* plan, const int32_t* verts,
+                     int32_t n_verts, int32_t first_valid, int32_t roi_x, int32_t roi_y, int32_t roi_w, int32_t roi_h,
+                     const float* taps, int32_t n_taps, int32_t dilate, float c, int32_t brighten, int32_t max_value,
+                     int32_t frames_per_batch, void* workspace, size_t workspace_bytes, void* stream);
+
 int ls_abi_version(void);
 const char* ls_last_error(void);
 

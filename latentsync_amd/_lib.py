@@ -147,6 +147,10 @@ _SIGS = {
     "ls_mjpeg_decode_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "ls_mjpeg_decode": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, C.c_int32, c_vp,
                                   C.c_int32, C.c_int32, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
+    "ls_face_brighten_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "ls_face_brighten": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, c_vp, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_int32, C.c_int32, C.c_int32, c_vp, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                   C.c_int32, C.c_int32, c_vp, C.c_size_t, c_vp]),
     "ls_add_rows":(C.c_int, [c_vp, C.c_int64, C.c_int32, C.c_int32, c_vp, C.c_int32, c_vp, C.c_int32, c_vp]),
 }
 

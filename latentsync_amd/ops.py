@@ -606,6 +606,50 @@ def mjpeg_decode(data, frames, H, W, quant, huff, max_segments=1, workspace=None
     return out, status
 
 
+def face_brighten(frames_u8, plan, verts, first_valid, roi, taps, dilate, c, brighten, max_value=235,
+                  frames_per_batch=0, workspace=None):
+    """The face brightness restore of use_darken requests (ls_face_brighten), in place on
+    uint8 RGB frames (n, H, W, 3) on the device; returns the tensor.  ``plan`` int32 (n, 4),
+    ``verts`` int32 (V, 2), ``first_valid``, ``roi`` = (x, y, w, h) and ``taps`` float32 are
+    darken.build_tables' / darken.gaussian_taps' (arrays or tensors; the layouts are in
+    include/ls_hip.h).  ``frames_per_batch``: frames whose masks are held at once (0: a fixed
+    budget).  ``workspace``: a caller's uint8 scratch tensor of at least
+    ls_face_brighten_workspace_bytes.  There is no CPU path."""
+    lib = _lib.load()
+    if (not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or
+            frames_u8.shape[-1] != 3 or not frames_u8.is_cuda):
+        raise ValueError("face_brighten: uint8 (n, H, W, 3) on the device expected, got "
+                         f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
+    if not frames_u8.is_contiguous():
+        raise ValueError("face_brighten: frames must be contiguous")
+    n, H, W, _ = frames_u8.shape
+    device = frames_u8.device
+    plan = torch.as_tensor(plan).to(device).contiguous()
+    verts = torch.as_tensor(verts).to(device).contiguous()
+    taps = torch.as_tensor(taps).to(device).contiguous()
+    if plan.dtype != torch.int32 or tuple(plan.shape) != (n, 4):
+        raise ValueError(f"face_brighten: plan must be int32 {(n, 4)}, got {plan.dtype} {tuple(plan.shape)}")
+    if verts.dtype != torch.int32 or verts.dim() != 2 or verts.shape[1] != 2 or verts.shape[0] < 1:
+        raise ValueError(f"face_brighten: verts must be int32 (V, 2), got {verts.dtype} {tuple(verts.shape)}")
+    if taps.dtype != torch.float32 or taps.dim() != 1:
+        raise ValueError(f"face_brighten: taps must be float32 (n_taps,), got {taps.dtype} {tuple(taps.shape)}")
+    if n == 0:
+        return frames_u8
+    rx, ry, rw, rh = (int(v) for v in roi)
+    fpb = int(frames_per_batch)
+    with torch.cuda.device(device):
+        need = lib.ls_face_brighten_workspace_bytes(n, rh, rw, fpb)
+        if workspace is None:
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+        elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != device:
+            raise ValueError("face_brighten: workspace must be a contiguous uint8 tensor on the frames' device")
+        check(lib.ls_face_brighten(_p(frames_u8), n, H, W, _p(plan), _p(verts), verts.shape[0], int(first_valid),
+                                   rx, ry, rw, rh, _p(taps), taps.numel(), int(dilate), float(c), int(bool(brighten)),
+                                   int(max_value), fpb, _p(workspace), workspace.numel(), _stream()),
+              "ls_face_brighten")
+    return frames_u8
+
+
 def prep_pixels(faces_u8, mask, ld=8, pix=None, masked=None):
     lib = _lib.load()
     F_, _, R, _ = faces_u8.shape

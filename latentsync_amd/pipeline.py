@@ -520,18 +520,33 @@ class LipsyncPipeline:
         any PCM or IEEE-float WAV, at any sample rate and channel count: it is decoded
         on the host and converted to mono at ``audio_sample_rate`` (for the .npz) and at
         16 kHz (for Whisper) on the device, as ffmpeg does for the reference
-        (util.py:103-112, whisper/audio.py:22-50); compressed audio is out of scope.  With
+        (util.py:103-112, whisper/audio.py:22-50); compressed audio is out of scope.
+        ``use_darken`` with a ``brightness_factor`` brightens the restored frames on the
+        device before they are written (write_video's enhance_face_brightness,
+        util.py:150-151; darken.py) and needs ``face_landmarks``: a .npy path or a float32
+        (N, P, 2) array of FaceMesh's normalised (x, y), one row per frame of data.pth, NaN
+        where no face was detected.  With
         ``faces_only=True`` (or a video_path that is not an array file) the
         lip-synced aligned faces are written instead and no warp-back happens."""
         from . import repeat as rep
         # write_video's brightness restore runs only `if use_darken and brightness_factor`
-        # (util.py:150-151, reached from :594); it needs the video writer and a face-mesh
-        # model this build does not carry, so exactly that case is refused.  Otherwise the
-        # factor is ignored, as the reference ignores it.
+        # (util.py:150-151, reached from :594).  It runs on the device (darken.py) from the
+        # caller's per-frame FaceMesh landmarks -- the face-mesh model is not carried -- so
+        # without them exactly that case is refused.  Otherwise the factor is ignored, as
+        # the reference ignores it.
+        landmarks = None
         if use_darken and brightness_factor:
-            raise NotImplementedError("use_darken with a brightness_factor: the video writer's face brightness "
-                                      "restore (darken_restore.enhance_face_brightness) is out of scope "
-                                      "(SURVEY.md §8(f)3)")
+            if kwargs.get("face_landmarks") is None:
+                raise NotImplementedError("use_darken with a brightness_factor: the video writer's face brightness "
+                                          "restore (darken_restore.enhance_face_brightness) needs the per-frame "
+                                          "FaceMesh landmarks, which this build cannot detect: pass face_landmarks= "
+                                          "(a .npy path or a float32 (N, P, 2) array of normalised x, y; a frame "
+                                          "without a face is a row of NaN)")
+            if kwargs.get("faces_only"):
+                raise ValueError("use_darken with faces_only=True: the brightness restore works on the restored "
+                                 "frames and face_landmarks are in frame coordinates")
+            from . import darken
+            landmarks = darken.load_landmarks(kwargs["face_landmarks"])
         # the reference casts to weight_dtype (fp16 on CUDA, scripts/inference.py:33-34); this
         # path computes in bf16 storage / fp32 accumulation for either half type
         if weight_dtype not in (torch.float16, torch.bfloat16):
@@ -545,6 +560,8 @@ class LipsyncPipeline:
             raise NotImplementedError("face detection / alignment is out of scope: pass data_path (.pth)")
         data = load_data_pth(data_path)
         faces, boxes, affine_matrices = data["faces"], list(data["boxes"]), list(data["affine_matrices"])
+        if landmarks is not None and len(landmarks) != len(faces):
+            raise ValueError(f"face_landmarks: {len(landmarks)} landmark rows for {len(faces)} faces in {data_path}")
         # the original frames are read up front (:405) because they are repeated /
         # truncated together with the faces, boxes and matrices below; only rank 0
         # restores and writes, so the other ranks never decode or hold them
@@ -552,6 +569,9 @@ class LipsyncPipeline:
         video_frames = None
         if rank0 and not kwargs.get("faces_only"):
             video_frames = read_video_frames(video_path, video_fps, self.device)
+        if landmarks is not None and rank0 and video_frames is None:
+            raise ValueError(f"use_darken: {video_path} yields no frames, so there are no restored frames to "
+                             "brighten (face_landmarks are in frame coordinates)")
         R = height or faces.shape[-1]
         self.check_inputs(R, width or R, callback_steps)
         # faces stored at another resolution are resized to R in run_windows, as the
@@ -566,8 +586,10 @@ class LipsyncPipeline:
 
         def per_frame(fn, n):
             """Apply a repeat/truncate to every per-frame sequence together (:448-452, :462-466)."""
-            nonlocal faces, boxes, affine_matrices, video_frames
+            nonlocal faces, boxes, affine_matrices, video_frames, landmarks
             faces, boxes, affine_matrices = fn(faces, n), fn(boxes, n), fn(affine_matrices, n)
+            if landmarks is not None:
+                landmarks = fn(landmarks, n)
             if video_frames is not None:
                 video_frames = fn(video_frames, n)
 
@@ -593,6 +615,13 @@ class LipsyncPipeline:
         frames_out = out_u8
         if video_frames is not None:
             frames_out = self.restore_video(out, video_frames, boxes, affine_matrices)
+            if landmarks is not None:
+                # write_video enhances every frame and the mux trims afterwards (:594-602); the
+                # recurrence is causal, so brightening before the trim below is equivalent
+                from . import darken
+                n_fr = frames_out.shape[0]
+                frames_out = darken.enhance_face_brightness(frames_out.contiguous(), np.asarray(landmarks[:n_fr]),
+                                                            brightness_factor)
         n_out = frames_out.shape[0]
         if video_out_path.endswith(".avi"):
             # a playable file: Motion-JPEG encoded on the device + PCM audio (video.py).  An

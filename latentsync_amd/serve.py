@@ -102,6 +102,12 @@ def run_job(pipeline, payload: dict, data_dir: str, results_dir: str, resolution
         raise ValueError(f"output_format must be 'npz' or 'avi', got {fmt!r}")
     video_out_path = os.path.join(results_dir, f"{payload['id']}.{fmt}")
     kw = {} if weight_dtype is None else dict(weight_dtype=weight_dtype)
+    # the brightness restore of a use_darken request needs the clip's FaceMesh landmarks
+    # (pipeline.py); they are prepared offline next to the data file.  Without the file the
+    # call is as before and the pipeline refuses the request.
+    landmarks_path = data_path[:-len(".pth")] + ".landmarks.npy"
+    if payload.get("use_darken") and os.path.exists(landmarks_path):
+        kw["face_landmarks"] = landmarks_path
     pipeline(video_path=video_path, audio_path=audio_path, video_out_path=video_out_path,
              video_mask_path=os.path.join(results_dir, f"{payload['id']}_mask.npz"), num_frames=16, num_inference_steps=20,
              guidance_scale=1.5, width=resolution, height=resolution, data_path=data_path,
