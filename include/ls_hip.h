@@ -77,7 +77,13 @@ enum { LS_ACT_NONE = 0, LS_ACT_GEGLU = 1, LS_ACT_GELU = 2, LS_ACT_SILU = 3 };
  *        rowvec_mod 0 = no modulo)
  *   v = (v + res[m, n]) * out_scale                      (residual, resnet.py:221)
  *   act: GEGLU pairs packed columns (32b+i, 32b+16+i) -> out col 16b+i,
- *        out = h * gelu_erf(g) (diffusers GEGLU); GELU (whisper MLP); SiLU.
+ *        out = h * gelu_erf(g) (diffusers GEGLU), N % 32 == 0, bias only: GEGLU with a
+ *        rowvec, a residual or an out_scale other than 1 is LS_ERR_INVALID;
+ *        GELU (whisper MLP); SiLU.
+ * N, ldy and ldr need not be multiples of 8: when N % 8, ldy % 8 or (with a residual)
+ * ldr % 8 is non-zero, the tiled kernels store element by element instead of 16 bytes at
+ * a time (bias, rowvec, residual and output are then only read / written below column N).
+ * C1, C2, ld1 and ld2 must be multiples of 8 (LS_ERR_INVALID otherwise).
  * split_k > 1 needs `workspace` of split_k*M*N fp32 (ls_conv_workspace_bytes).
  */
 typedef struct {
@@ -372,20 +378,28 @@ int ls_timestep_embed_f32(const float* ts, int32_t B, int32_t dim, int32_t flip,
  * [n_steps][4] = {sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev)} read at
  * *step; then *step += 1 (single thread).  When guidance > 1 the batch halves are
  * (uncond, audio).  unet_in (bf16 NHWC [Bu*P][ld_in]) receives the new latents in
- * channels 0..3 of every batch copy.
+ * channels 0..3 of every batch copy (8-byte stores: ld_in % 4 == 0, unet_in 8-B aligned;
+ * channels 4.. of unet_in are left as they are).
+ * LS_ERR_INVALID, nothing launched: null pointers, Bu other than 1 or 2, P < 1,
+ * ld_eps < 4, ld_in < 4 or not a multiple of 4.
  */
 int ls_ddim_cfg_step(const uint16_t* eps, int32_t ld_eps, int32_t Bu, int64_t P, float guidance, float* lat,
                      const float* coef, int32_t* step, uint16_t* unet_in, int32_t ld_in, void* stream);
 
 /* Pixel prep (ImageProcessor.preprocess_fixed_mask_image image_processor.py:145-152):
  * faces uint8 NCHW [F][3][R][R]; mask fp32 [R][R] (1 = keep);
- * pix / masked bf16 NHWC [F][R][R][ld] (channels 3..ld-1 zeroed). */
+ * pix / masked bf16 NHWC [F][R][R][ld] (channels 3..ld-1 zeroed; ld 8 takes 16-byte
+ * stores and needs 16-B aligned pix / masked).
+ * LS_ERR_INVALID, nothing launched: null pointers, F < 1, R < 1, ld < 3. */
 int ls_prep_pixels(const uint8_t* faces, int32_t F, int32_t R, const float* mask, uint16_t* pix, uint16_t* masked,
                    int32_t ld, void* stream);
 
 /* DiagonalGaussianDistribution.sample + (z - shift) * scaling (lipsync_pipeline.py:296-297):
  * moments fp32 NHWC [P][ld_m] (mean = ch 0..3, logvar = ch 4..7), eps fp32 [P][4];
- * writes bf16 into dst[P][ld_dst] at channel offset c_off. */
+ * writes bf16 into dst[P][ld_dst] at channel offset c_off (channels c_off..c_off+3; the
+ * others are left as they are).  logvar is clamped to [-30, 20] as the reference does.
+ * LS_ERR_INVALID, nothing launched: null pointers, P < 1, ld_m < 8, c_off < 0 or
+ * c_off + 4 > ld_dst. */
 int ls_vae_sample(const float* moments, int32_t ld_m, const float* eps, int64_t P, float scaling, float shift,
                   uint16_t* dst, int32_t ld_dst, int32_t c_off, void* stream);
 
@@ -393,23 +407,35 @@ int ls_vae_sample(const float* moments, int32_t ld_m, const float* eps, int64_t 
  * (lipsync_pipeline.py:517-549): ch 4 = nearest-resized keep-mask (prepare_mask_latents
  * :290), ch 5..8 masked-image latents, ch 9..12 reference latents (both already
  * written by ls_vae_sample into `cond` [P][16]); replicated into Bu copies of
- * unet_in [Bu][P][ld_in] together with the initial latents lat fp32 [P][4]. */
+ * unet_in [Bu][P][ld_in] together with the initial latents lat fp32 [P][4]; channels
+ * 13..15 are zeroed, channels 16.. left as they are (P = F h h; two 16-byte stores per
+ * pixel: unet_in 16-B aligned).
+ * LS_ERR_INVALID, nothing launched: null pointers, F, R, h or Bu < 1, ld_in < 16 or not a
+ * multiple of 8. */
 int ls_pack_unet_input(const float* lat, const uint16_t* cond, const float* mask, int32_t F, int32_t R, int32_t h,
                        int32_t Bu, uint16_t* unet_in, int32_t ld_in, void* stream);
 
 /* decode_latents prep (lipsync_pipeline.py:146-147): z = lat / scaling + shift,
- * lat fp32 [P][4] -> bf16 NHWC [P][ld]. */
+ * lat fp32 [P][4] -> bf16 NHWC [P][ld] (channels 4..ld-1 zeroed; ld 8 takes 16-byte
+ * stores and needs a 16-B aligned z).
+ * LS_ERR_INVALID, nothing launched: null pointers, P < 1, ld < 4. */
 int ls_scale_latents(const float* lat, int64_t P, float inv_scaling, float shift, uint16_t* z, int32_t ld,
                      void* stream);
 
 /* paste_surrounding_pixels_back + pixel_values_to_images (lipsync_pipeline.py:327-341):
  * out = dec * (1 - keep) + pix * keep; dec / pix bf16 NHWC [F][R][R][ld*];
- * out_nchw fp32 [F][3][R][R] (may be NULL), out_u8 uint8 [F][R][R][3] (may be NULL). */
+ * out_nchw fp32 [F][3][R][R] (may be NULL), out_u8 uint8 [F][R][R][3] (may be NULL):
+ * out_u8 = trunc(clamp(out / 2 + 0.5, 0, 1) * 255).
+ * LS_ERR_INVALID, nothing launched: null inputs, both outputs NULL, F < 1, R < 1, a pitch
+ * below 3. */
 int ls_paste_back(const uint16_t* dec, int32_t ld_dec, const uint16_t* pix, int32_t ld_pix, const float* mask,
                   int32_t F, int32_t R, float* out_nchw, uint8_t* out_u8, void* stream);
 
 /* y[r, c] = x[r, c] + table[r % table_rows, c] (table fp32 [table_rows][C]): the
- * whisper positional-embedding add (whisper/model.py:155). */
+ * whisper positional-embedding add (whisper/model.py:155).  x / y rows are ldx / ldy elements
+ * apart; columns C.. of y are left as they are.
+ * LS_ERR_INVALID, nothing launched: null pointers, rows, C or table_rows < 1, ldx < C,
+ * ldy < C. */
 int ls_add_rows(const uint16_t* x, int64_t rows, int32_t C, int32_t ldx, const float* table, int32_t table_rows,
                 uint16_t* y, int32_t ldy, void* stream);
 

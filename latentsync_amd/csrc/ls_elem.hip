@@ -272,8 +272,9 @@ extern "C" int ls_small_linear(const float* x, int32_t M, int32_t K, const uint1
 extern "C" int ls_ddim_cfg_step(const uint16_t* eps, int32_t ld_eps, int32_t Bu, int64_t P, float guidance,
                                 float* lat, const float* coef, int32_t* step, uint16_t* unet_in, int32_t ld_in,
                                 void* stream) {
-  if (!eps || !lat || !coef || !step || !unet_in || (Bu != 1 && Bu != 2) || ld_eps < 4 || ld_in < 4 || ld_in % 4)
-    return fail(LS_ERR_INVALID, "ls_ddim_cfg_step: bad arguments");
+  if (!eps || !lat || !coef || !step || !unet_in || (Bu != 1 && Bu != 2) || P <= 0 || ld_eps < 4 || ld_in < 4 ||
+      ld_in % 4)
+    return fail(LS_ERR_INVALID, "ls_ddim_cfg_step: bad arguments (Bu 1 or 2, P > 0, ld_eps >= 4, ld_in >= 4, % 4)");
   hipStream_t s = (hipStream_t)stream;
   ddim_cfg_kernel<<<cdiv(P, 256), 256, 0, s>>>(eps, ld_eps, Bu, P, guidance, lat, coef, step, unet_in, ld_in);
   int rc = check_launch("ddim_cfg_kernel");
@@ -284,7 +285,8 @@ extern "C" int ls_ddim_cfg_step(const uint16_t* eps, int32_t ld_eps, int32_t Bu,
 
 extern "C" int ls_prep_pixels(const uint8_t* faces, int32_t F, int32_t R, const float* mask, uint16_t* pix,
                               uint16_t* masked, int32_t ld, void* stream) {
-  if (!faces || !mask || !pix || !masked || ld < 3) return fail(LS_ERR_INVALID, "ls_prep_pixels: bad arguments");
+  if (!faces || !mask || !pix || !masked || ld < 3 || F <= 0 || R <= 0)
+    return fail(LS_ERR_INVALID, "ls_prep_pixels: bad arguments (F > 0, R > 0, ld >= 3)");
   const long n = (long)F * R * R;
   prep_pixels_kernel<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(faces, F, R, mask, pix, masked, ld);
   return check_launch("prep_pixels_kernel");
@@ -292,7 +294,8 @@ extern "C" int ls_prep_pixels(const uint8_t* faces, int32_t F, int32_t R, const 
 
 extern "C" int ls_vae_sample(const float* moments, int32_t ld_m, const float* eps, int64_t P, float scaling,
                              float shift, uint16_t* dst, int32_t ld_dst, int32_t c_off, void* stream) {
-  if (!moments || !eps || !dst || ld_m < 8) return fail(LS_ERR_INVALID, "ls_vae_sample: bad arguments");
+  if (!moments || !eps || !dst || ld_m < 8 || P <= 0 || c_off < 0 || c_off + 4 > ld_dst)
+    return fail(LS_ERR_INVALID, "ls_vae_sample: bad arguments (P > 0, ld_m >= 8, 0 <= c_off, c_off + 4 <= ld_dst)");
   vae_sample_kernel<<<cdiv(P, 256), 256, 0, (hipStream_t)stream>>>(moments, ld_m, eps, P, scaling, shift, dst, ld_dst,
                                                                     c_off);
   return check_launch("vae_sample_kernel");
@@ -300,7 +303,8 @@ extern "C" int ls_vae_sample(const float* moments, int32_t ld_m, const float* ep
 
 extern "C" int ls_pack_unet_input(const float* lat, const uint16_t* cond, const float* mask, int32_t F, int32_t R,
                                   int32_t h, int32_t Bu, uint16_t* unet_in, int32_t ld_in, void* stream) {
-  if (!lat || !cond || !mask || !unet_in || ld_in % 8 || ld_in < 16) return fail(LS_ERR_INVALID, "ls_pack_unet_input");
+  if (!lat || !cond || !mask || !unet_in || ld_in % 8 || ld_in < 16 || F <= 0 || R <= 0 || h <= 0 || Bu <= 0)
+    return fail(LS_ERR_INVALID, "ls_pack_unet_input: bad arguments (F, R, h, Bu > 0, ld_in >= 16, % 8)");
   const long P = (long)F * h * h;
   pack_unet_input_kernel<<<cdiv(P, 256), 256, 0, (hipStream_t)stream>>>(lat, cond, mask, F, R, h, Bu, unet_in, ld_in);
   return check_launch("pack_unet_input_kernel");
@@ -308,14 +312,15 @@ extern "C" int ls_pack_unet_input(const float* lat, const uint16_t* cond, const 
 
 extern "C" int ls_scale_latents(const float* lat, int64_t P, float inv_s, float shift, uint16_t* z, int32_t ld,
                                 void* stream) {
-  if (!lat || !z || ld < 4) return fail(LS_ERR_INVALID, "ls_scale_latents: bad arguments");
+  if (!lat || !z || ld < 4 || P <= 0) return fail(LS_ERR_INVALID, "ls_scale_latents: bad arguments (P > 0, ld >= 4)");
   scale_latents_kernel<<<cdiv(P, 256), 256, 0, (hipStream_t)stream>>>(lat, P, inv_s, shift, z, ld);
   return check_launch("scale_latents_kernel");
 }
 
 extern "C" int ls_paste_back(const uint16_t* dec, int32_t ld_dec, const uint16_t* pix, int32_t ld_pix,
                              const float* mask, int32_t F, int32_t R, float* out, uint8_t* out_u8, void* stream) {
-  if (!dec || !pix || !mask || (!out && !out_u8)) return fail(LS_ERR_INVALID, "ls_paste_back: bad arguments");
+  if (!dec || !pix || !mask || (!out && !out_u8) || F <= 0 || R <= 0 || ld_dec < 3 || ld_pix < 3)
+    return fail(LS_ERR_INVALID, "ls_paste_back: bad arguments (F > 0, R > 0, pitches >= 3, one output)");
   const long n = (long)F * R * R;
   paste_back_kernel<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(dec, ld_dec, pix, ld_pix, mask, F, R, out, out_u8);
   return check_launch("paste_back_kernel");
@@ -323,7 +328,8 @@ extern "C" int ls_paste_back(const uint16_t* dec, int32_t ld_dec, const uint16_t
 
 extern "C" int ls_add_rows(const uint16_t* x, int64_t rows, int32_t C, int32_t ldx, const float* table,
                            int32_t table_rows, uint16_t* y, int32_t ldy, void* stream) {
-  if (!x || !table || !y || table_rows <= 0) return fail(LS_ERR_INVALID, "ls_add_rows: bad arguments");
+  if (!x || !table || !y || table_rows <= 0 || rows <= 0 || C <= 0 || ldx < C || ldy < C)
+    return fail(LS_ERR_INVALID, "ls_add_rows: bad arguments (rows, C, table_rows > 0, ldx >= C, ldy >= C)");
   const long n = rows * C;
   add_rows_kernel<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(x, rows, C, ldx, table, table_rows, y, ldy);
   return check_launch("add_rows_kernel");

@@ -3018,6 +3018,9 @@ static int build_args(const ls_conv_desc* d, ConvArgs& a, TileCfg& t, int& split
   if (d->ksize == 1 && (d->Ho != d->H || d->Wo != d->W || d->stride != 1 || d->upsample))
     return fail(LS_ERR_INVALID, "ls_conv2d: ksize 1 must be stride 1 with no resampling");
   if (d->act == LS_ACT_GEGLU && (d->N % 32)) return fail(LS_ERR_INVALID, "ls_conv2d: GEGLU needs N % 32 == 0");
+  // (the GEGLU epilogues -- epi_geglu8, store_tile_geglu, the row-block kernel's -- add the bias only)
+  if (d->act == LS_ACT_GEGLU && (d->rowvec || d->res || (d->out_scale != 0.f && d->out_scale != 1.f)))
+    return fail(LS_ERR_INVALID, "ls_conv2d: GEGLU takes no rowvec, residual or out_scale");
   if (d->aff_scale && (!d->aff_shift || d->imgs_per_sample <= 0))
     return fail(LS_ERR_INVALID, "ls_conv2d: affine prologue needs shift and imgs_per_sample");
   if (d->rowvec && d->rows_per_vec <= 0) return fail(LS_ERR_INVALID, "ls_conv2d: rowvec needs rows_per_vec");
@@ -3052,6 +3055,9 @@ static int build_args(const ls_conv_desc* d, ConvArgs& a, TileCfg& t, int& split
     static const int tb[11][2] = {{0, 0}, {128, 128}, {128, 64}, {64, 64}, {128, 32}, {256, 256}, {256, 128},
                                   {257, 256}, {258, 256}, {128, 160}, {259, 160}};
     t.bm = tb[g_force_tile][0]; t.bn = tb[g_force_tile][1]; t.split = g_force_split ? g_force_split : 1;
+    // the 256-row kernels have no register-staged form (affine prologue, tuning key 1): such a
+    // call runs a 128-row kernel, and the grid below must be the one of the kernel launched
+    if (t.bm >= 256 && (d->aff_scale || g_force_regstage)) { t.bm = 128; t.bn = 128; }
   }
 #ifdef LS_DIAG_KERNELS
   if (g_t256 && !g_force_tile && d->ksize == 1 && a.ktiles <= 20 && d->N % 128 == 0 && !d->aff_scale &&
