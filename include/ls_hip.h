@@ -60,6 +60,21 @@ enum { LS_ACT_NONE = 0, LS_ACT_GEGLU = 1, LS_ACT_GELU = 2, LS_ACT_SILU = 3 };
  * stride 2 + pad 1 = Downsample3D (resnet.py:89), stride 2 + pad 0 = the SD-VAE
  * downsampler after F.pad(0,1,0,1); upsample = nearest x2 fused into the
  * gather (Upsample3D, resnet.py:53-73).
+ * upsample = 1: Wp is the ordinary 9-tap 3x3 operand.  upsample = 2: the same layer with
+ * PHASE-PACKED weights.  The 2 x 2 output pixels of an input pixel read one 3 x 3 input
+ * neighbourhood, and the three row taps of output parity py land on two input rows
+ * (py = 0: rows y-1, y with weights w[0], w[1]+w[2]; py = 1: rows y, y+1 with weights
+ * w[0]+w[1], w[2]; the same in x), so the layer is four 2x2 convs over the input image, one
+ * per parity ph = 2 py + px, 4/9 of the multiply-adds.  Wp is then [4][N][K], K = 4*Cin,
+ * k = (ci / 64) * 256 + (2 dy + dx) * 64 + ci % 64 (latentsync_amd/packing.py,
+ * pack_phase_weight: taps summed in fp32, rounded once).  It needs ksize 3, Cin % 64 == 0,
+ * stride 1, pad 1, Ho x Wo = 2H x 2W and no affine prologue (else LS_ERR_INVALID).  It runs
+ * on the halo-tile kernel (ls_conv_path 4: H and W multiples of 16, N % 160 or % 128 == 0,
+ * 16 < N <= 640, one source) or else on the tiled kernels (ls_conv_path 5: per parity a pad-1
+ * conv in input space over 4 of the 9 tap positions, the parity a grid slice; one source, no
+ * rowvec, no activation, bf16 output, N % 8 == 0, ldy % 8 == 0, no split-K; gn_colsum_out by a
+ * read pass).  ls_conv_path answers -1 elsewhere (ls_conv2d then fails with LS_ERR_INVALID:
+ * callers keep upsample = 1 for those shapes).
  *
  * Wp is the packed weight [N][K]: K = ksize*ksize*Cin rounded up to 64, in the same
  * k order: tap-major, except ksize 3 with Cin % 64 == 0, which is channel-chunk-major
@@ -128,7 +143,9 @@ int ls_conv2d(const ls_conv_desc* d, void* stream);
  * 3 = halo-tile 3x3 conv (ABI 12: 3x3 / stride 1 / pad 1 (or a nearest-x2 upsample without an
  * input affine, round 6), Cin % 64 == 0, W in {16, 32,
  * 64} or a multiple of 64, N % 160 or % 128 == 0; takes the GroupNorm affine + SiLU on
- * its input, once per pixel, and the dual-source concat), -1 = invalid descriptor.
+ * its input, once per pixel, and the dual-source concat), 4 = the halo-tile kernel's phase
+ * form (upsample = 2), 5 = the tiled kernels' phase form (upsample = 2), -1 = invalid
+ * descriptor or upsample = 2 with no phase-form kernel.
  * Host-only, no launch. */
 int ls_conv_path(const ls_conv_desc* d);
 size_t ls_conv_workspace_bytes(const ls_conv_desc* d);

@@ -36,6 +36,12 @@ struct ConvArgs {
                // 16 = skip MFMAs (DMA kernel)
   int ccm;     // 3x3 with Cin % 64 == 0: K is channel-chunk-major, taps innermost (see tap_of)
   int gm;      // tile raster: groups of gm row-blocks x all column tiles, row-block fastest (tile_of)
+  int Mo;      // rows of y (== M except in the tiled phase form, where M counts one parity's rows)
+  // tiled phase form of an upsample conv (ls_conv_desc.upsample == 2 off the halo kernel): 0, or
+  // 1 + ph for output parity ph = 2 py + px.  The launch is a plain pad-1 conv in INPUT space
+  // (Ho x Wo = H x W, M = n_img H W) over the parity's 4 taps with its [N][4 Cin] weights; the
+  // host passes 1 and a 4 x larger grid, the kernel sets ph (EPI_PLAINP, tile_phase)
+  int phase;
 };
 
 // Logical tile index -> (row-block, column-block), grouped: gm row-blocks x all ntn column
@@ -59,6 +65,11 @@ __device__ __forceinline__ void tile_of(const ConvArgs& a, int bid, int& tm, int
 // Returns the tap and sets c0 = the K-tile's first input channel (k0 = a 64-aligned or,
 // for BK 32, 32-aligned K offset).
 __device__ __forceinline__ int tap_of(const ConvArgs& a, int k0, int& c0) {
+  if (a.phase) {  // k = (ci / 64) * 256 + t * 64 + ci % 64: 3x3 tap (py + t / 2, px + t % 2)
+    const int t = (k0 >> 6) & 3, ph = a.phase - 1;
+    c0 = (k0 >> 8) * 64 + (k0 & 63);
+    return ((ph >> 1) + (t >> 1)) * 3 + (ph & 1) + (t & 1);
+  }
   if (a.ccm) {
     const int chunk = k0 / 576, rem = k0 - chunk * 576;
     c0 = chunk * 64 + (rem & 63);
@@ -262,9 +273,17 @@ struct EpiSide {
 };
 
 // tile-local row -> output row (RW: see store_tile_plain)
+constexpr int RW_PHASE = -(1 << 20);  // the tiled phase form: rows are one parity's pixels in input space
 template <int RW>
 __device__ __forceinline__ int epi_out_row(const ConvArgs& a, int m0, long m0r, int lr) {
-  if constexpr (RW > 0) return (int)(m0r + (long)(lr / RW) * a.Wo + lr % RW);
+  if constexpr (RW == RW_PHASE) {  // input pixel (n, y, x) of parity (py, px) -> (n Ho + 2y + py) Wo + 2x + px
+    const int m = m0 + lr;
+    if (m >= a.M) return a.Mo;  // (past the parity's rows: not stored)
+    const int hw = a.H * a.W, n = m / hw, r = m - n * hw;
+    const int y = r / a.W, x = r - y * a.W, ph = a.phase - 1;
+    return ((n * 2 * a.H + 2 * y + (ph >> 1)) * 2 * a.W + 2 * x + (ph & 1));
+  } else if constexpr (RW > 0) return (int)(m0r + (long)(lr / RW) * a.Wo + lr % RW);
+  else if constexpr (RW < 0) return (int)(m0r + (long)(lr / -RW) * 2 * a.Wo + 2 * (lr % -RW));
   else return m0 + lr;
 }
 
@@ -281,7 +300,7 @@ __device__ __forceinline__ void epi_side_load(const ConvArgs& a, int m0, int n0,
 #pragma unroll
   for (int it = 0; it < G::ITER; ++it) {
     const int rl = r0 + it * G::RPI, row = epi_out_row<RW>(a, m0, m0r, p * G::WTM + rl);
-    const bool ok = cok && rl < G::WTM && row < a.M;
+    const bool ok = cok && rl < G::WTM && row < a.Mo;
     sd.rs[it] = make_uint4(0, 0, 0, 0);
     if (ok && a.res) sd.rs[it] = *(const uint4*)(a.res + (long)row * a.ldr + col);
   }
@@ -290,7 +309,9 @@ __device__ __forceinline__ void epi_side_load(const ConvArgs& a, int m0, int n0,
 // CSF: the column sums also for a 256-row tile whose wave rows are 64 (the halo conv);
 // RW > 0: the tile's rows are BM / RW segments of RW consecutive output pixels, one per
 // image row (the halo conv's TH x TW tiles); m0 is then the tile's VIRTUAL first row
-// (GroupNorm slots) and m0r the real first row.  PRE: pass 0's side inputs were loaded by
+// (GroupNorm slots) and m0r the real first row.  RW < 0 (the phase form of an upsample conv):
+// the segments are -RW INPUT pixels of one input row, i.e. every second pixel of every second
+// output row from m0r (one output parity).  PRE: pass 0's side inputs were loaded by
 // the caller (epi_side_load during its last K-tile) into `pre`.  Pass p + 1's side inputs
 // are issued right after pass p's staging barrier, so only the first pass waits on HBM.
 // CSG > 1 (round 6, the halo convs): the column sums are kept per thread in registers -- its
@@ -324,7 +345,7 @@ __device__ __forceinline__ void store_tile_plain_pre(const ConvArgs& a, f32x4 (&
   // row vector (per-frame temb / positional-encoding rows): one row for the whole
   // tile in the common case (rows_per_vec >= the tile's row span), folded into
   // the per-column constants; otherwise looked up per row.
-  const bool rv_tile = a.rowvec && out_row(0) / a.rows_per_vec == (RW > 0 ? out_row(BM - 1)
+  const bool rv_tile = a.rowvec && out_row(0) / a.rows_per_vec == (RW != 0 ? out_row(BM - 1)
                                                                            : min(m0 + BM, a.M) - 1) / a.rows_per_vec;
   float bb[8], cs[8];
 #pragma unroll
@@ -353,7 +374,7 @@ __device__ __forceinline__ void store_tile_plain_pre(const ConvArgs& a, f32x4 (&
     for (int it = 0; it < ITER; ++it) {
       const int rl = r0 + it * RPI, row = out_row(p * WTM + rl);
       mr[it] = make_float2(0.f, 1.f);
-      if (cok && rl < WTM && row < a.M && a.ln_mr) mr[it] = *(const float2*)(a.ln_mr + 2L * row);
+      if (cok && rl < WTM && row < a.Mo && a.ln_mr) mr[it] = *(const float2*)(a.ln_mr + 2L * row);
     }
     __syncthreads();
     EpiSide<ITER> nxt;
@@ -361,7 +382,7 @@ __device__ __forceinline__ void store_tile_plain_pre(const ConvArgs& a, f32x4 (&
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
       const int rl = r0 + it * RPI, row = out_row(p * WTM + rl);
-      if (!(cok && rl < WTM && row < a.M)) continue;
+      if (!(cok && rl < WTM && row < a.Mo)) continue;
       const float* s = st + rl * SP + c8;
       const float4 s0 = *(const float4*)s, s1 = *(const float4*)(s + 4);
       float v[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
@@ -539,7 +560,20 @@ __device__ __forceinline__ void store_tile_geglu(const ConvArgs& a, f32x4 (&acc)
 //              residual / LayerNorm fold as runtime options);
 //   EPI_GEGLU: the same for the GEGLU epilogue;
 //   EPI_ANY:   everything (split-K slabs, GELU/SiLU, fp32 out, ragged N).
-enum { EPI_PLAIN = 0, EPI_GEGLU = 1, EPI_ANY = 2 };
+//   EPI_PLAINP: EPI_PLAIN for the tiled phase form of an upsample conv: the block's parity is
+//              its grid slice (tile_phase) and the rows go through epi_out_row<RW_PHASE>.
+enum { EPI_PLAIN = 0, EPI_GEGLU = 1, EPI_ANY = 2, EPI_PLAINP = 3 };
+
+// EPI_PLAINP: the grid is 4 x ntm x ntn (no split-K), the slice index z is the parity: point the
+// kernel's own copy of the arguments at the parity's weights and rows
+template <int EPI>
+__device__ __forceinline__ void tile_phase(ConvArgs& a, int& z) {
+  if constexpr (EPI == EPI_PLAINP) {
+    a.w += (long)z * a.N * a.K;
+    a.phase = 1 + z;
+    z = 0;
+  }
+}
 
 template <int BM, int BN, int WM, int WN, int EPI = EPI_ANY>
 __device__ __forceinline__ void store_tile(const ConvArgs& a, f32x4 (&acc)[BM / WM / 16][BN / WN / 16], float* st,
@@ -550,6 +584,9 @@ __device__ __forceinline__ void store_tile(const ConvArgs& a, f32x4 (&acc)[BM / 
     return;
   } else if constexpr (EPI == EPI_GEGLU) {
     store_tile_geglu<BM, BN, WM, WN, false>(a, acc, st, m0, n0);
+    return;
+  } else if constexpr (EPI == EPI_PLAINP) {  // (no column sums: the host runs the read pass)
+    store_tile_plain<BM, BN, WM, WN, false, false, RW_PHASE>(a, acc, st, m0, n0);
     return;
   }
   constexpr int NT = WM * WN * 64;
@@ -872,6 +909,13 @@ struct BufDma {
       k.tap = 0;
       k.two = a.C2 && kt * 64 >= a.C1;  // concat: a K-tile lies in one source (host: C1 % 64 == 0)
       k.soff_a = k.two ? (kt * 64 - a.C1) * 2 : kt * 128;
+    } else if (a.phase) {  // (uniform) the parity's 4 taps per chunk: tap and channel straight from kt
+      int cc;
+      k.tap = tap_of(a, kt * 64, cc);
+      const int kh = k.tap / 3, kw = k.tap - kh * 3;
+      k.two = cc >= a.C1;
+      const int ld = k.two ? a.ld2 : a.ld1;
+      k.soff_a = ((kh * a.W + kw) * ld + (k.two ? cc - a.C1 : cc)) * 2;
     } else {
       if (c0 == 0 && tap == 0 && kt != 0) tap = tap_of(a, kt * 64, c0);
       const int kh = tap / 3, kw = tap - kh * 3;
@@ -958,9 +1002,10 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_dma_kernel(ConvArgs a)
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
   const int nt = a.ntm * a.ntn;
-  int bid = xcd_remap(blockIdx.x, nt * a.split);
-  const int z = bid / nt;
+  int bid = xcd_remap(blockIdx.x, nt * (EPI == EPI_PLAINP ? 4 : a.split));
+  int z = bid / nt;
   bid -= z * nt;
+  tile_phase<EPI>(a, z);
   int tm, tn;
   tile_of(a, bid, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
@@ -1371,9 +1416,10 @@ __global__ void __launch_bounds__(512) conv_gemm_big_kernel(ConvArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
   const int nt = a.ntm * a.ntn;
-  int bid = xcd_remap(blockIdx.x, nt * a.split);
-  const int z = bid / nt;
+  int bid = xcd_remap(blockIdx.x, nt * (EPI == EPI_PLAINP ? 4 : a.split));
+  int z = bid / nt;
   bid -= z * nt;
+  tile_phase<EPI>(a, z);
   int tm, tn;
   tile_of(a, bid, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
@@ -2315,17 +2361,28 @@ struct HaloCfg {
 // are in flight per thread
 __host__ __device__ constexpr int hb_lo(int b, int nhl) { return b == 0 ? 0 : b == 1 ? (nhl + 2) / 3 : b == 2 ? (2 * nhl + 2) / 3 : nhl; }
 // VMEM instructions a thread issues after the weight DMA at tap t (0..8) of a chunk:
-// the halo batch loaded there (+ its 4 affine loads) when a next chunk exists
 // the halo batch loaded there (+ at tap 0 the chunk's affine parameters, one float4 per thread)
-__host__ __device__ constexpr int halo_issue(int t, int nhl, bool gn) {
-  return t == 0 ? hb_lo(1, nhl) + (gn ? 1 : 0) : t == 3 ? hb_lo(2, nhl) - hb_lo(1, nhl) : t == 6 ? nhl - hb_lo(2, nhl) : 0;
+// (ts: taps between two batches -- 3 with 9 taps per chunk, 1 with the phase form's 4)
+__host__ __device__ constexpr int halo_issue(int t, int nhl, bool gn, int ts = 3) {
+  return t == 0 ? hb_lo(1, nhl) + (gn ? 1 : 0) : t == ts ? hb_lo(2, nhl) - hb_lo(1, nhl) : t == 2 * ts ? nhl - hb_lo(2, nhl) : 0;
 }
 
 // Halo pieces: the (TH + 2) x (TW + 2) pixels the taps read x 8 16-B chunks (2592 pieces at
 // 16 x 16: 5.06 per thread); piece j of a thread has its own LDS slot hdst[j].
-template <int TW, int BN, bool GN, bool CSF, int TH_ = 256 / TW>
+// PH (the phase form of a nearest-x2 upsample conv, ls_conv_desc.upsample == 2): the block
+// owns a TH x TW patch of the INPUT image and one output parity ph = 2 py + px (a grid
+// dimension).  The 2 x 2 output pixels of an input pixel read the same 3 x 3 input
+// neighbourhood, and the three row (column) taps of parity py (px) land on two input rows
+// (columns), so the parity's outputs are a 2 x 2 conv over the plain input-space halo image:
+// 4 taps per chunk, tap t at halo offset (py + t / 2, px + t % 2), with the phase's own
+// summed weights ([4][N][4 Cin], K-tile 4 ci + t; packing.pack_phase_weight); the epilogue
+// stores patch pixel (r, c) at output pixel (2 (y0 + r) + py, 2 (x0 + c) + px).
+template <int TW, int BN, bool GN, bool CSF, int TH_ = 256 / TW, bool PH = false>
 __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, TH_>::MINB)) conv3x3_halo_kernel(ConvArgs a) {
   using HC = HaloCfg<TW, BN, TH_>;
+  static_assert(!(PH && GN), "the phase form takes no input affine");
+  constexpr int NTAP = PH ? 4 : 9;  // taps per chunk
+  constexpr int TS = PH ? 1 : 3;    // taps between two halo batches
   constexpr int TH = HC::TH, P = HC::P, HALO = HC::HALO, WSLOT = HC::WSLOT, NSW = HC::NSW, NT = HC::NT;
   constexpr int WNW = HC::WNW;
   constexpr bool COMPACT = HC::COMPACT;
@@ -2347,19 +2404,27 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
   int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int tn = bid % ntn;
   bid /= ntn;
+  int ph = 0;  // (the four parities of a patch run next to each other: they read the same input)
+  if constexpr (PH) {
+    ph = bid & 3;
+    bid >>= 2;
+  }
+  const int py = ph >> 1, px = ph & 1;
   const int txb = bid % tpr;
   bid /= tpr;
   const int tyb = bid % tpc;
   const int img = bid / tpc;
   const int y0 = tyb * TH, x0 = txb * TW, n0 = tn * BN;
-  const long HW = (long)a.H * a.W;  // the OUTPUT image (for an upsample conv the launch passes the output dims)
+  // the image the patches tile: the output image (for a 9-tap upsample conv the launch passes the
+  // output dims); in the phase form the INPUT image (H x W as given, upsample zeroed by the launch)
+  const long HW = (long)a.H * a.W;
   // nearest x2 upsample (round 6): halo pixel (y, x) of the output image reads input pixel
   // (y >> 1, x >> 1) -- the LDS halo image, the taps and the epilogue are those of a plain conv
   const int ups = a.upsample;
   const int Wi = a.W >> ups;
   const long HWi = HW >> (2 * ups);
   const int nchunk = a.Cin / 64;
-  const int G = 9 * nchunk;  // taps in all
+  const int G = NTAP * nchunk;  // taps in all
 
   // ---- this thread's halo pieces: q = j*NT + tid -> read pixel q / 8 (row-major over the
   // (TH + 2) x (TW + 2) pixels the taps read), logical 16-B chunk tid & 7; its slot in the
@@ -2392,7 +2457,8 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
   const long aff0 = (long)img * HW / a.pix_per_sample * a.Cin;
   // weight descriptor from column n0 (rows n0 + BN > N -- the narrow tile over N = 8 -- lie
   // past it and read zeros)
-  const i32x4 rs_w = buffer_rsrc(a.w + (long)n0 * a.K, (uint32_t)min((long)min(BN, a.N - n0) * a.K * 2, (long)cap));
+  // (phase form: the parity's [N][K] matrix)
+  const i32x4 rs_w = buffer_rsrc(a.w + ((long)ph * a.N + n0) * a.K, (uint32_t)min((long)min(BN, a.N - n0) * a.K * 2, (long)cap));
   uint4 hreg[HB];
   float4 gp;
   // the affine parameters of chunk ci (64 scales, 64 shifts): every thread loads one float4
@@ -2447,7 +2513,7 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
   };
   auto store_halo = [&](int buf, int b) { put_halo(buf, hb_lo(b, NHL), hb_lo(b + 1, NHL), hreg); };
 
-  // ---- weight DMA: tap g = 9 ci + t is K-tile g of the channel-chunk-major packing
+  // ---- weight DMA: tap g = NTAP ci + t is K-tile g of the channel-chunk-major packing
   // (buffer-descriptor DMA from column n0: per thread one byte offset, per tap the uniform
   // soffset g * 128 -- no 64-bit address arithmetic in the tap loop)
   int wvo[DPT];
@@ -2460,7 +2526,9 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
   // ring slot of tap g: with 3 slots, (9 ci + t) % 3 == t % 3 is known per tap at compile time
   // (2 slots: (9 ci + t) % 2 == (ci + t) % 2, so with the chunk parity par = ci & 1 computed
   // once per chunk the slot of every tap is one of two per-chunk values -- no per-tap g % 2)
-  auto wslot = [&](int par, int t) { return NSW == 3 ? t % 3 : (t & 1) ^ par; };
+  // (phase form, 4 taps per chunk: 2 slots t % 2; 3 slots (4 ci + t) % 3 = (ci + t) % 3 from
+  // the per-chunk par = ci % 3)
+  auto wslot = [&](int par, int t) { return PH ? (NSW == 3 ? (par + t) % 3 : t & 1) : NSW == 3 ? t % 3 : (t & 1) ^ par; };
   const int wid_u = __builtin_amdgcn_readfirstlane(wid);
   __builtin_assume(wid_u >= 0 && wid_u < NT / 64);
   // (LDS destinations as 32-bit LDS-space addresses: a generic-pointer select cast to LDS
@@ -2481,7 +2549,8 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
   // fragment i is patch row 4 wm + i, column l16)
   static_assert(TW == 16, "fragment i = one patch row");
   const int p0 = 64 * wm + l16;
-  const int hp0 = (p0 / TW) * P + (p0 % TW) + (COMPACT ? 0 : 3);  // halo pixel of fragment 0 at tap (0, 0)
+  // halo pixel of fragment 0 at tap (0, 0) (phase form: at the parity's first tap (py, px))
+  const int hp0 = (p0 / TW) * P + (p0 % TW) + (COMPACT ? 0 : 3) + py * P + px;
 
   f32x4 acc[FM][FN];
 #pragma unroll
@@ -2510,10 +2579,11 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
 
   bf16x8 apf[2][FM];  // A fragments of the current tap (both k-steps)
   auto read_a = [&](const uint4* hb, int tt) {  // (tt compile-time after inlining)
-    const int hpt = hp0 + (tt / 3) * P + tt % 3;
+    constexpr int TPR = PH ? 2 : 3;  // taps per kernel row
+    const int hpt = hp0 + (tt / TPR) * P + tt % TPR;
     // the swizzle phase, shared by the wave's fragments: padded rows (P == 0 mod 8) the
     // pixel's, compact rows the halo column's (l16 + kw)
-    const int sw = COMPACT ? (l16 + tt % 3) & 7 : hpt & 7;
+    const int sw = COMPACT ? (l16 + px + tt % TPR) & 7 : hpt & 7;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       const int base = hpt * 8 + ((ks * 4 + lg) ^ sw);
@@ -2525,11 +2595,15 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
   auto tap = [&](int ci, int par, auto t_tag, auto last_tag) {
     constexpr int t = decltype(t_tag)::value;
     constexpr bool LAST = decltype(last_tag)::value;  // no next chunk
-    const int g = 9 * ci + t;
+    const int g = NTAP * ci + t;
+    const int hpar = ci & 1;  // the chunk's halo image (par: the weight ring's per-chunk value)
     // the weight DMA of tap g landed: VMEM instructions younger than it are the weights
     // of the NSW - 2 later taps and the halo batches issued at taps t - NSW + 1 .. t - 1
-    constexpr int HY = LAST ? 0 : (t - 1 >= 0 ? halo_issue(t - 1, NHL, GN) : 0) +
-                                  (NSW >= 3 && t - 2 >= 0 ? halo_issue(t - 2, NHL, GN) : 0);
+    // (HY only counts what may stay in flight behind the weights.  The halo registers themselves
+    // are plain buffer loads: store_halo's use of them gets the compiler's own vmcnt wait -- in
+    // the phase form already one tap after the load -- so no counted wait has to cover them)
+    constexpr int HY = LAST ? 0 : (t - 1 >= 0 ? halo_issue(t - 1, NHL, GN, TS) : 0) +
+                                  (NSW >= 3 && t - 2 >= 0 ? halo_issue(t - 2, NHL, GN, TS) : 0);
     if (g + NSW - 2 >= G) wait_vm<0>();  // the ring's tail
     else wait_vm<(NSW - 2) * DPT + HY>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -2538,10 +2612,10 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
     if (g + NSW - 1 < G) issue_w(g + NSW - 1, wslot(par, t + NSW - 1));
     if constexpr (!LAST) {
       if constexpr (GN && t == 1) store_par(ci + 1);  // read at taps 3 / 6 / 8, past a barrier
-      if constexpr (t == 3 || t == 6) store_halo(par ^ 1, t / 3 - 1);
-      if constexpr (t == 0 || t == 3 || t == 6) load_halo(ci + 1, t / 3);
+      if constexpr (t == TS || t == 2 * TS) store_halo(hpar ^ 1, t / TS - 1);
+      if constexpr (t == 0 || t == TS || t == 2 * TS) load_halo(ci + 1, t / TS);
     }
-    const uint4* hb = hbuf + par * HALO;
+    const uint4* hb = hbuf + hpar * HALO;
     const uint4* wb = wbuf + wslot(par, t) * WSLOT;
     // A fragments of tap t: at t = 0 read here; for t > 0 read at the end of tap t - 1 (the
     // halo image is stable within a chunk), so after this tap's barrier only the weight
@@ -2560,8 +2634,8 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
         for (int j = 0; j < FN; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(apf[ks][i], bfr[j], acc[i][j], 0, 0, 0);
     }
-    if constexpr (t < 8) read_a(hb, t + 1);
-    if constexpr (!LAST && t == 8) store_halo(par ^ 1, 2);
+    if constexpr (t < NTAP - 1) read_a(hb, t + 1);
+    if constexpr (!LAST && t == NTAP - 1) store_halo(hpar ^ 1, 2);
   };
   using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
   using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
@@ -2569,10 +2643,13 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
   using I6 = std::integral_constant<int, 6>; using I7 = std::integral_constant<int, 7>;
   using I8 = std::integral_constant<int, 8>;
   auto chunk = [&](int ci, auto last) {
-    const int par = ci & 1;
+    const int par = PH && NSW == 3 ? ci % 3 : ci & 1;
     tap(ci, par, I0{}, last); tap(ci, par, I1{}, last); tap(ci, par, I2{}, last);
-    tap(ci, par, I3{}, last); tap(ci, par, I4{}, last); tap(ci, par, I5{}, last);
-    tap(ci, par, I6{}, last); tap(ci, par, I7{}, last); tap(ci, par, I8{}, last);
+    tap(ci, par, I3{}, last);
+    if constexpr (!PH) {
+      tap(ci, par, I4{}, last); tap(ci, par, I5{}, last);
+      tap(ci, par, I6{}, last); tap(ci, par, I7{}, last); tap(ci, par, I8{}, last);
+    }
   };
   for (int ci = 0; ci + 1 < nchunk; ++ci) chunk(ci, std::false_type{});
   chunk(nchunk - 1, std::true_type{});
@@ -2580,11 +2657,14 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   // epilogue: virtual rows (GroupNorm slots) = the patch's index within its image x 256
-  const int m0v = (int)(img * HW) + (tyb * tpr + txb) * (TH * TW);
-  const long m0r = img * HW + (long)y0 * a.W + x0;
+  // (phase form: the output image has 4 HW pixels; the block's TH x TW stored pixels fill the
+  // slots of patch (ph, tyb, txb) -- every output pixel once, every slot 128 stored rows)
+  const int m0v = PH ? (int)(img * 4 * HW) + ((ph * tpc + tyb) * tpr + txb) * (TH * TW)
+                     : (int)(img * HW) + (tyb * tpr + txb) * (TH * TW);
+  const long m0r = PH ? img * 4 * HW + (long)(2 * y0 + py) * a.Wo + 2 * x0 + px : img * HW + (long)y0 * a.W + x0;
   // column sums from per-thread register partials (CSG = 2: store_tile_plain_pre's slot-end form)
   static_assert((size_t)(NT / (BN / 8)) * BN * 2 * 4 <= (size_t)2 * HALO * 16, "column-sum partials fit the halo images");
-  store_tile_plain<TH * TW, BN, TH / 4, WNW, false, CSF, TW, 2>(a, acc, (float*)lds_dyn, m0v, n0, m0r);
+  store_tile_plain<TH * TW, BN, TH / 4, WNW, false, CSF, PH ? -TW : TW, 2>(a, acc, (float*)lds_dyn, m0v, n0, m0r);
 }
 
 // ---------------------------------------------------------------- host side
@@ -2760,6 +2840,7 @@ static bool launch_rowblock(const ConvArgs& a0, hipStream_t s) {
 
 // epilogue variant of a launch (see store_tile)
 static int epi_kind(const ConvArgs& a) {
+  if (a.phase) return EPI_PLAINP;  // (tiled_phase_ok: the plain epilogue's conditions hold)
   const bool vec = (a.N % 8 == 0) && (a.ldy % 8 == 0) && (!a.res || a.ldr % 8 == 0);
   if (a.split != 1 || !vec || a.y_f32) return EPI_ANY;
   if (a.act == LS_ACT_NONE) return EPI_PLAIN;
@@ -2835,6 +2916,9 @@ static void launch_dma(const ConvArgs& a, int grid, hipStream_t s) {
       }
     }
 #endif
+    if constexpr (KS == 3 && TAPU) {  // the tiled phase form (tiled_phase_ok: buffer-descriptor DMA)
+      if (a.phase) { launch_dma1<BM, BN, WM, WN, KS, TAPU, 2, 64, EPI_PLAINP, true>(a, grid, s); return; }
+    }
     if (buf_dma_ok(a, KS)) {
       switch (epi_kind(a)) {
         case EPI_PLAIN: launch_dma1<BM, BN, WM, WN, KS, TAPU, 2, 64, EPI_PLAIN, true>(a, grid, s); return;
@@ -2859,6 +2943,9 @@ static void launch_big2(const ConvArgs& a, int grid, hipStream_t s) {
 
 template <int BN, int KS, bool TAPU>
 static void launch_big1(const ConvArgs& a, int grid, hipStream_t s) {
+  if constexpr (KS == 3 && TAPU) {
+    if (a.phase) { launch_big2<BN, KS, TAPU, EPI_PLAINP, true>(a, grid, s); return; }
+  }
   if constexpr (KS == 1 || TAPU) {
     if (buf_dma_ok(a, KS)) {
       switch (epi_kind(a)) {
@@ -2926,7 +3013,7 @@ static bool g_halo_narrow = true;
 // patch width of the halo conv for this call (0: not taken)
 static int halo_tw(const ls_conv_desc* d, const ConvArgs& a) {
   if (!g_halo || g_force_tile || g_force_regstage || d->ksize != 3 || a.stride != 1 || a.pad != 1 ||
-      !a.ccm || a.Cin % 64 || a.C1 % 64 || a.K != 9 * a.Cin || a.y_f32 || a.act != LS_ACT_NONE ||
+      !a.ccm || a.Cin % 64 || a.C1 % 64 || a.K != (a.upsample == 2 ? 4 : 9) * a.Cin || a.y_f32 || a.act != LS_ACT_NONE ||
       a.ln_mr || a.stats_out || a.ldy % 8 || (a.res && a.ldr % 8))
     return 0;
   // nearest x2 upsample (Upsample3D, resnet.py:53-71; round 6): no input affine (the UNet's
@@ -2944,19 +3031,21 @@ static int halo_tw(const ls_conv_desc* d, const ConvArgs& a) {
   if (((uintptr_t)a.x1 | (uintptr_t)a.x2 | (uintptr_t)a.w) & 15 || a.ld1 % 8 || (a.C2 && a.ld2 % 8)) return 0;
   // 16 x 16 patches everywhere: the smallest halo overhead ((16 + 2)^2 / 256 = 1.27 input
   // pixels per output pixel; 32 x 8: 1.33, 64 x 4: 1.55) and no register spills
-  const int tw = (a.Wo % 16 == 0 && a.Ho % 16 == 0) ? 16 : 0;
+  // (the phase form of an upsample conv, upsample == 2, patches the INPUT image)
+  const int tw = (a.upsample == 2 ? a.W % 16 == 0 && a.H % 16 == 0 : a.Wo % 16 == 0 && a.Ho % 16 == 0) ? 16 : 0;
   if (!tw) return 0;
+  if (a.upsample == 2 && (a.N <= 16 || a.C2)) return 0;  // (no narrow tile, one source)
   if ((long)a.H * a.W * a.ld1 * 2 >= (1L << 31) || (a.C2 && (long)a.H * a.W * a.ld2 * 2 >= (1L << 31)))
     return 0;  // per-image buffer descriptors
   return tw;
 }
 
-template <int TW, int BN, bool GN, bool CSF, int TH>
+template <int TW, int BN, bool GN, bool CSF, int TH, bool PH = false>
 static void launch_halo3(const ConvArgs& a, hipStream_t s) {
   using HC = HaloCfg<TW, BN, TH>;
-  const int ntile = a.n_img * (a.H / HC::TH) * (a.W / TW) * ((a.N + BN - 1) / BN);
-  LS_SET_MAX_DYN_SHM((conv3x3_halo_kernel<TW, BN, GN, CSF, TH>), HC::SHM);
-  conv3x3_halo_kernel<TW, BN, GN, CSF, TH><<<ntile, HC::NT, HC::SHM, s>>>(a);
+  const int ntile = a.n_img * (a.H / HC::TH) * (a.W / TW) * ((a.N + BN - 1) / BN) * (PH ? 4 : 1);
+  LS_SET_MAX_DYN_SHM((conv3x3_halo_kernel<TW, BN, GN, CSF, TH, PH>), HC::SHM);
+  conv3x3_halo_kernel<TW, BN, GN, CSF, TH, PH><<<ntile, HC::NT, HC::SHM, s>>>(a);
 }
 
 template <int TW, int BN, int TH = 256 / TW>
@@ -2985,8 +3074,30 @@ static void launch_halo1(const ConvArgs& a, hipStream_t s) {
   else launch_halo2<TW, 128>(a, s);
 }
 
+// the phase form (upsample == 2): input-space patches, the output parity a grid dimension;
+// the same tile choice as launch_halo1 (H, W here the input image)
+static void launch_halo_phase(const ConvArgs& a, hipStream_t s) {
+  ConvArgs o = a;
+  o.upsample = 0;  // (the kernel's halo image is the plain input-space one)
+  const bool cs = a.cs_out != nullptr;
+  if (a.N % 160 == 0 && !(g_halo_bn128 && a.N % 128 == 0)) {
+    if (cs) launch_halo3<16, 160, false, true, 16, true>(o, s);
+    else launch_halo3<16, 160, false, false, 16, true>(o, s);
+  } else if (g_halo_th8 && a.Cin <= 256) {
+    if (cs) launch_halo3<16, 128, false, true, 8, true>(o, s);
+    else launch_halo3<16, 128, false, false, 8, true>(o, s);
+  } else {
+    if (cs) launch_halo3<16, 128, false, true, 16, true>(o, s);
+    else launch_halo3<16, 128, false, false, 16, true>(o, s);
+  }
+}
+
 static void launch_halo(const ConvArgs& a, int tw, hipStream_t s) {
   (void)tw;  // (16: the only patch width compiled)
+  if (a.upsample == 2) {
+    launch_halo_phase(a, s);
+    return;
+  }
   if (a.upsample) {  // the kernel works in output space: H, W = the output image
     ConvArgs o = a;
     o.H = a.Ho;
@@ -3005,6 +3116,27 @@ static int g_t256 = ls_env("LS_GEMM_T256") ? atoi(ls_env("LS_GEMM_T256")) : 0;
 
 #endif  // LS_DIAG_KERNELS
 
+// The phase form of an upsample conv (upsample == 2) on the tiled kernels, for what the halo
+// kernel does not take (N > 640, images its patches do not divide): per output parity a plain
+// pad-1 conv in input space over 4 of the 9 tap positions (BufDma's border masks and tap_of
+// as for any 3x3), the parity a grid slice, rows mapped to the strided output pixels in the
+// plain epilogue (EPI_PLAINP); GroupNorm column sums by the read pass over the stored output.
+static bool tiled_phase_ok(const ls_conv_desc* d, const ConvArgs& a, const TileCfg& t) {
+  const bool vec = (a.N % 8 == 0) && (a.ldy % 8 == 0) && (!a.res || a.ldr % 8 == 0);
+  return d->upsample == 2 && vec && !a.y_f32 && a.act == LS_ACT_NONE && !a.rowvec && !a.C2 && !g_force_regstage &&
+         t.bm <= 256 && buf_dma_ok(a, 3);
+}
+
+static void to_tiled_phase(ConvArgs& a, const TileCfg& t) {
+  a.phase = 1;  // (the kernel sets 1 + ph)
+  a.upsample = 0;
+  a.Ho = a.H;
+  a.Wo = a.W;
+  a.M = a.n_img * a.H * a.W;
+  a.ntm = cdiv(a.M, t.bm);
+  a.gm = std::max(1, std::min(a.gm, a.ntm));
+}
+
 static int build_args(const ls_conv_desc* d, ConvArgs& a, TileCfg& t, int& split) {
   if (!d || !d->x1 || !d->w || !d->y) return fail(LS_ERR_INVALID, "ls_conv2d: null pointer");
   if (d->ksize != 1 && d->ksize != 3) return fail(LS_ERR_INVALID, "ls_conv2d: ksize must be 1 or 3");
@@ -3012,7 +3144,12 @@ static int build_args(const ls_conv_desc* d, ConvArgs& a, TileCfg& t, int& split
   if (d->C1 % 8 || d->C2 % 8 || Cin <= 0) return fail(LS_ERR_INVALID, "ls_conv2d: channels must be multiples of 8");
   if (d->C2 && !d->x2) return fail(LS_ERR_INVALID, "ls_conv2d: C2 > 0 needs x2");
   if (d->ld1 % 8 || (d->C2 && d->ld2 % 8)) return fail(LS_ERR_INVALID, "ls_conv2d: pixel pitch must be a multiple of 8");
-  const long Kneed = (long)d->ksize * d->ksize * Cin;
+  if (d->upsample < 0 || d->upsample > 2) return fail(LS_ERR_INVALID, "ls_conv2d: upsample must be 0, 1 or 2");
+  if (d->upsample == 2 && (d->ksize != 3 || Cin % 64 || d->K != 4 * Cin || d->aff_scale || d->stride != 1 ||
+                           d->pad != 1 || d->Ho != 2 * d->H || d->Wo != 2 * d->W))
+    return fail(LS_ERR_INVALID, "ls_conv2d: upsample 2 (phase-packed weights) needs ksize 3, Cin % 64 == 0, K == 4 Cin, "
+                                "no affine prologue, stride 1, pad 1, Ho x Wo = 2H x 2W");
+  const long Kneed = (d->upsample == 2 ? 4L : (long)d->ksize * d->ksize) * Cin;
   if (d->K % 64 || d->K < Kneed || d->K - Kneed >= 64 + (d->ksize == 3 ? 0 : 0))
     return fail(LS_ERR_INVALID, "ls_conv2d: K must be ksize^2*Cin rounded up to 64");
   if (d->ksize == 1 && (d->Ho != d->H || d->Wo != d->W || d->stride != 1 || d->upsample))
@@ -3031,7 +3168,7 @@ static int build_args(const ls_conv_desc* d, ConvArgs& a, TileCfg& t, int& split
   a.stride = d->stride; a.pad = d->pad; a.upsample = d->upsample;
   a.aff_scale = d->aff_scale; a.aff_shift = d->aff_shift;
   a.pix_per_sample = d->imgs_per_sample * d->H * d->W; a.silu_in = d->silu_in;
-  a.w = d->w; a.K = d->K; a.N = d->N; a.M = (int)M; a.CC = Cin / 8;
+  a.w = d->w; a.K = d->K; a.N = d->N; a.M = (int)M; a.Mo = (int)M; a.phase = 0; a.CC = Cin / 8;
   a.bias = d->bias; a.rowvec = d->rowvec; a.rows_per_vec = d->rows_per_vec; a.rowvec_mod = d->rowvec_mod;
   a.ln_mr = d->ln_rowstats; a.ln_cs = d->ln_colsum;
   if (a.ln_mr && (!a.ln_cs || d->ksize != 1)) return fail(LS_ERR_INVALID, "ls_conv2d: ln_rowstats needs ln_colsum, ksize 1");
@@ -3049,7 +3186,7 @@ static int build_args(const ls_conv_desc* d, ConvArgs& a, TileCfg& t, int& split
   a.ccm = (d->ksize == 3 && Cin % 64 == 0) ? 1 : 0;
   a.gm = 1;  // (set with the tile below)
   a.ktiles = d->K / 64;
-  t = pick_tile(M, d->N, a.ktiles, d->split_k <= 0 && d->workspace != nullptr,
+  t = pick_tile(M, d->N, a.ktiles, d->split_k <= 0 && d->workspace != nullptr && d->upsample != 2,
                 !d->aff_scale && !g_force_regstage && (d->ksize == 1 || Cin % 64 == 0), d->ksize);
   if (g_force_tile) {
     static const int tb[11][2] = {{0, 0}, {128, 128}, {128, 64}, {64, 64}, {128, 32}, {256, 256}, {256, 128},
@@ -3075,7 +3212,7 @@ static int build_args(const ls_conv_desc* d, ConvArgs& a, TileCfg& t, int& split
   // LS_GEMM_GM_SHORTK=0
   if (g_gemm_gm <= 0 && g_gm_shortk && t.bm == 256 && t.bn == 256 && d->ksize == 1 && d->K <= 1920) a.gm = 4;
   a.gm = std::max(1, std::min(a.gm, a.ntm));
-  split = d->split_k > 0 ? d->split_k : t.split;
+  split = d->upsample == 2 ? 1 : d->split_k > 0 ? d->split_k : t.split;  // (the phase forms have no split-K)
   split = std::min(split, a.ktiles);
   a.kt_per_split = cdiv(a.ktiles, split);
   split = cdiv(a.ktiles, a.kt_per_split);
@@ -3184,12 +3321,18 @@ extern "C" int ls_conv2d(const ls_conv_desc* d, void* stream) {
     if (split > 1) a.partial = (float*)d->workspace;
   }
   hipStream_t s = (hipStream_t)stream;
-  if (const int tw = halo_tw(d, a)) {  // 3x3 from an LDS halo tile, input affine fused, with the column sums
+  const bool tphase = a.upsample == 2 && !halo_tw(d, a);
+  if (tphase) {  // the phase form on the tiled kernels (callers ask ls_conv_path first: 5)
+    if (!tiled_phase_ok(d, a, t))
+      return fail(LS_ERR_INVALID, "ls_conv2d: no phase-form kernel for this shape (ls_conv_path -1): use upsample = 1");
+    to_tiled_phase(a, t);
+  }
+  if (const int tw = tphase ? 0 : halo_tw(d, a)) {  // 3x3 from an LDS halo tile, input affine fused, with the column sums
     launch_halo(a, tw, s);
     return check_launch("conv3x3_halo_kernel");
   }
   float* cs = a.cs_out;  // GroupNorm column sums: epilogue (tiled / row-block) or a trailing read pass
-  if (rowblock_ok(d, a)) {
+  if (!tphase && rowblock_ok(d, a)) {
     if (launch_rowblock(a, s)) return check_launch("gemm_rowblock_kernel");  // with cs_out if given
     a.cs_out = nullptr;  // no row-block instance with the sums: without them, then a read pass
     if (cs && launch_rowblock(a, s)) {
@@ -3207,13 +3350,13 @@ extern "C" int ls_conv2d(const ls_conv_desc* d, void* stream) {
     return ls_row_stats((const uint16_t*)d->y, d->ldy, a.M, d->N, a.stats_eps, so, stream);
   }
   const bool tapu = (d->ksize == 3) && (a.Cin % 64 == 0);
-  const int grid = a.ntm * a.ntn * a.split;
+  const int grid = a.ntm * a.ntn * (tphase ? 4 : a.split);
   // epilogue column sums: single-pass vectorised epilogue and a tile whose staging
   // buffer holds the per-thread partials (cs_tile_fits; not 128x32 / 64x64)
   const bool vec = (a.N % 8 == 0) && (a.ldy % 8 == 0) && (!a.res || a.ldr % 8 == 0);
   // (not the 256-row kernels: compiled in, the sums cost their main loop ~12 % -- they run
   // at the 256-VGPR limit -- against a ~15 us read pass; same-box A/B, scripts/ab_lib.sh)
-  const bool cs_epi = cs && a.split == 1 && vec && !(t.bm == 128 && t.bn == 32) && t.bm != 64 &&
+  const bool cs_epi = cs && !tphase && a.split == 1 && vec && !(t.bm == 128 && t.bn == 32) && t.bm != 64 &&
                       (t.bm < 256 || (t.bm == 260 && epi_kind(a) == EPI_PLAIN));
   if (cs_epi) a.cs_out = cs;
 #ifdef LS_DIAG_KERNELS
@@ -3246,7 +3389,7 @@ extern "C" int ls_conv2d(const ls_conv_desc* d, void* stream) {
     splitk_reduce_kernel<<<cdiv(nchunk, 256), 256, 0, s>>>(a);
     if ((rc = check_launch("splitk_reduce_kernel")) != LS_OK) return rc;
   }
-  if (cs && !cs_epi) return launch_colsum_pass((const u16*)d->y, d->ldy, a.M, d->N, cs, s);
+  if (cs && !cs_epi) return launch_colsum_pass((const u16*)d->y, d->ldy, a.Mo, d->N, cs, s);
   return LS_OK;
 }
 
@@ -3254,6 +3397,7 @@ extern "C" int ls_conv_path(const ls_conv_desc* d) {
   ConvArgs a; TileCfg t; int split;
   if (build_args(d, a, t, split) != LS_OK) return -1;
   a.cs_out = nullptr;  // (the column sums never change the path)
+  if (a.upsample == 2) return halo_tw(d, a) ? 4 : tiled_phase_ok(d, a, t) ? 5 : -1;
   int ntm, ntn;
   if (rowblock_ok(d, a) && rowblock_flags(a, &ntm, &ntn) >= 0) return 1;
   if (halo_tw(d, a)) return 3;

@@ -16,6 +16,8 @@ from ._lib import check
 ACT_NONE, ACT_GEGLU, ACT_GELU, ACT_SILU = 0, 1, 2, 3
 _GN_EPILOGUE = _lib.ab_switch("LS_GN_EPILOGUE", "1") != "0"  # A/B switch (diagnostics): 0 = GN stats by read pass
 GN_SLOT_ROWS = 128  # LS_GN_SLOT_ROWS
+# A/B switch (diagnostics): 0 = upsample convs with phase-packed weights (Packed.phase) stay on the 9-tap form
+_UPS_PHASE = _lib.ab_switch("LS_UPS_PHASE", "1") != "0"
 
 
 def _p(t):
@@ -56,6 +58,9 @@ class Packed:
         self.geglu = geglu
         self.colsum = None  # set for LayerNorm-folded weights (unet._Dev.packed_ln)
         self.pe_rows = None  # W pe table for a folded LayerNorm + positional encoding
+        # bf16 [4][N][4 cin]: the phase-packed form of a 3x3 weight (packing.pack_phase_weight)
+        # for conv(..., upsample=True); w stays the 9-tap operand for the shapes it cannot take
+        self.phase = None
 
 
 def _ld(t):
@@ -73,7 +78,8 @@ def _ld(t):
 
 def conv_path(x, pw: Packed, **kw):
     """Which kernel family ls_conv2d takes for this call (ls_conv_path: 0 tiled, 1 row-block,
-    2 register-staged, 3 halo-tile 3x3) -- host only, nothing is launched."""
+    2 register-staged, 3 halo-tile 3x3, 4 / 5 the halo-tile / tiled phase form of an upsample
+    conv) -- host only, nothing is launched."""
     return conv(x, pw, _path_only=True, **kw)
 
 
@@ -84,6 +90,8 @@ def conv(x, pw: Packed, *, x2=None, aff=None, stride=1, pad=None, upsample=False
     aff = (scale[S][C], shift[S][C], imgs_per_sample, silu); rowvec = (t[S][ld], rows_per_vec, ld[, mod]);
     ln_stats = (mean, rstd) rows from row_stats(): LayerNorm folded into pw (pw.colsum);
     stats_out = fp32 (rows, 2) receiving row_stats() of the output (eps 1e-5);
+    upsample = nearest x2 before the 3x3: with pw.phase set, as four 2x2 phase convs
+    (ls_conv_desc.upsample = 2) where ls_conv_path takes that form (4, 5), else the 9-tap form;
     gn_out = also emit the output's GroupNorm column sums (ls_conv_desc.gn_colsum_out),
     attached to the result as `.gn_cs` for group_norm() (when rows % 128 == 0);
     aff_materialize = when the call would take the register-staged GEMM for the affine
@@ -133,6 +141,12 @@ def conv(x, pw: Packed, *, x2=None, aff=None, stride=1, pad=None, upsample=False
         assert stats_out.dtype == torch.float32 and stats_out.is_contiguous() and stats_out.numel() == 2 * n * Ho * Wo
         assert pw.n_out == pw.N and act != ACT_GEGLU, "row statistics over the real output channels only"
         d.row_stats_out, d.row_stats_eps = _p(stats_out), 1e-5
+    if upsample and pw.phase is not None and _UPS_PHASE and aff is None:
+        # the one decision: the library says whether this call has a phase-form kernel
+        # (4 halo-tile, 5 tiled); an input affine never has one, so it is not asked
+        d.upsample, d.w, d.K = 2, _p(pw.phase), pw.phase.shape[2]
+        if lib.ls_conv_path(C.byref(d)) not in (4, 5):
+            d.upsample, d.w, d.K = 1, _p(pw.w), pw.K
     if _path_only:
         return lib.ls_conv_path(C.byref(d))
     if aff is not None and aff_materialize and lib.ls_conv_path(C.byref(d)) == 2:

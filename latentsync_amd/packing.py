@@ -49,6 +49,43 @@ def pack_weight(w: torch.Tensor, cin_pad: int = None, n_pad: int = None) -> torc
     return w
 
 
+# output parity p (row or column) -> per 2x2 tap d in {0, 1} the 3x3 taps it sums: a nearest-x2
+# upsample followed by a 3x3 pad-1 conv reads, for output row 2y + p, input rows y - 1 + p + d
+PHASE_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))
+
+
+def phase_tap_sums(w: torch.Tensor) -> torch.Tensor:
+    """w (O, I, 3, 3) -> (4, O, I, 2, 2): per output parity ph = 2 py + px the 2x2 kernel whose
+    tap (dy, dx) is the sum of the 3x3 taps PHASE_TAPS[py][dy] x PHASE_TAPS[px][dx] (fp32, or
+    fp64 for an fp64 w)."""
+    w = w if w.dtype == torch.float64 else w.float()
+    O, I = w.shape[:2]
+    out = torch.zeros(4, O, I, 2, 2, dtype=w.dtype)
+    for py in range(2):
+        for px in range(2):
+            for dy in range(2):
+                for dx in range(2):
+                    for a in PHASE_TAPS[py][dy]:
+                        for b in PHASE_TAPS[px][dx]:
+                            out[2 * py + px, :, :, dy, dx] += w[:, :, a, b]
+    return out
+
+
+def pack_phase_weight(w: torch.Tensor) -> torch.Tensor:
+    """w (O, I, 3, 3), I % 64 == 0 -> fp32 (4, O, 4 I): the four 2x2 convs over the INPUT image
+    that equal conv3x3(nearest_x2(x), w, padding=1) (ls_conv_desc.upsample == 2,
+    include/ls_hip.h).  Phase ph = 2 py + px holds the weights of the output pixels
+    (2y + py, 2x + px); its tap t = 2 dy + dx reads input pixel (y - 1 + py + dy,
+    x - 1 + px + dx) (zero outside the image) with the sum of the 3x3 taps that land there
+    (PHASE_TAPS), summed in fp32 -- the caller rounds the sums to bf16 once.  K order
+    k = (ci / 64) * 256 + t * 64 + ci % 64: the four taps of a 64-channel chunk are
+    consecutive K-tiles, as the 9 of pack_weight's channel-chunk-major form."""
+    O, I, kh, kw = w.shape
+    assert kh == 3 and kw == 3 and I % 64 == 0, (tuple(w.shape),)
+    s = phase_tap_sums(w).reshape(4, O, I // 64, 64, 4)  # (ph, o, chunk, ci % 64, t)
+    return s.permute(0, 1, 2, 4, 3).reshape(4, O, 4 * I).contiguous()
+
+
 def pad_bias(b, n_pad=None):
     if b is None:
         return None

@@ -28,7 +28,7 @@ import torch
 
 from . import _lib, ops
 from .config import STAGE2_MODEL
-from .packing import geglu_interleave, pack_ff_w2, pack_weight, pad_bias
+from .packing import geglu_interleave, pack_ff_w2, pack_phase_weight, pack_weight, pad_bias
 from .schema import unet_param_shapes
 from .weights import fill_state_dict
 
@@ -124,7 +124,10 @@ class _Dev:
     def f32(self, key):
         return self.sd[key].float().to(self.device).contiguous()
 
-    def packed(self, wkey, bkey=None, ksize=None, cin_pad=None, n_pad=None, w=None, b=None, geglu=False):
+    def packed(self, wkey, bkey=None, ksize=None, cin_pad=None, n_pad=None, w=None, b=None, geglu=False,
+               phase=False):
+        """phase: also the phase-packed form of an upsampler's 3x3 (Packed.phase), when its
+        input channels are whole 64-channel chunks."""
         w = self.sd[wkey] if w is None else w
         b = (self.sd.get(bkey) if bkey else None) if b is None else b
         if ksize is None:
@@ -135,8 +138,11 @@ class _Dev:
         wp = pack_weight(w, cin_pad=cin_pad, n_pad=n_pad)
         bp = pad_bias(b, n_pad)
         cin = cin_pad or (w.shape[1] + 7) // 8 * 8
-        return ops.Packed(wp.to(torch.bfloat16).to(self.device).contiguous(),
-                          None if bp is None else bp.to(self.device).contiguous(), cin, ksize, n_out, geglu)
+        pk = ops.Packed(wp.to(torch.bfloat16).to(self.device).contiguous(),
+                        None if bp is None else bp.to(self.device).contiguous(), cin, ksize, n_out, geglu)
+        if phase and ksize == 3 and w.dim() == 4 and w.shape[1] % 64 == 0 and not cin_pad and not n_pad:
+            pk.phase = pack_phase_weight(w).to(torch.bfloat16).to(self.device).contiguous()
+        return pk
 
     def packed_ln(self, w, b, ln, geglu=False, pe=None):
         """nn.LayerNorm(gamma, beta) followed by linear(w, b), folded for the GEMM
@@ -405,8 +411,8 @@ class _DeviceUNet:
                 a = _Transformer(dv, f"{p}.attentions.{l}", out_c, rheads[i], groups, audio) \
                     if bt == "CrossAttnUpBlock3D" else None
                 layers.append((r, a, motion(f"{p}.motion_modules.{l}", out_c)))
-            us = dv.packed(f"up_blocks.{i}.upsamplers.0.conv.weight", f"up_blocks.{i}.upsamplers.0.conv.bias") \
-                if i < nb - 1 else None
+            us = dv.packed(f"up_blocks.{i}.upsamplers.0.conv.weight", f"up_blocks.{i}.upsamplers.0.conv.bias",
+                           phase=True) if i < nb - 1 else None
             self.up.append((layers, us))
         self.norm_out = (dv.f32("conv_norm_out.weight"), dv.f32("conv_norm_out.bias"))
         self.groups, self.eps = groups, eps

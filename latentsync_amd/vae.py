@@ -101,7 +101,7 @@ class _DeviceVAE:
         for i in range(len(boc)):
             res = [_Res(dv, f"decoder.up_blocks.{i}.resnets.{l}") for l in range(lpb + 1)]
             us = dv.packed(f"decoder.up_blocks.{i}.upsamplers.0.conv.weight",
-                           f"decoder.up_blocks.{i}.upsamplers.0.conv.bias") if i < len(boc) - 1 else None
+                           f"decoder.up_blocks.{i}.upsamplers.0.conv.bias", phase=True) if i < len(boc) - 1 else None
             self.dec.append((res, us))
         self.dec_norm = (dv.f32("decoder.conv_norm_out.weight"), dv.f32("decoder.conv_norm_out.bias"))
         # 8 output columns (3 used): the narrow halo-tile conv stores 16-B rows
