@@ -253,6 +253,7 @@ __global__ void __launch_bounds__(256) gn_apply_u_kernel(const u16* __restrict__
   const u16* src = c < C1 ? x1 + c : x2 + (c - C1);
   const int lds = c < C1 ? C1 : C2;
   const long p0 = (long)blockIdx.x * ppb * U + pl;
+  if (p0 >= n_pix) return;  // ragged last block: no pixel, so no sample whose scale / shift could be read
   uint4 v[U];
 #pragma unroll
   for (int k = 0; k < U; ++k) {

@@ -116,7 +116,7 @@ def geglu_bound(ref_h, b_h, ref_g, b_g, out_dtype):
     return ref, _slack(b)
 
 
-def attn_bound(q, k, v, scale, q_prescaled=False):
+def attn_bound(q, k, v, scale, q_prescaled=False, q_err=None, k_err=None, v_err=None):
     """(ref, B) in fp64 for o = softmax(scale q k^T) v; q (..., nq, d), k / v (..., nk, d).
 
         B = 2^-8 |ref| + (2 2^-8 + 2 expm1(delta) + (nk + 4) 2^-23) sum_j p_j |v_j|
@@ -136,6 +136,12 @@ def attn_bound(q, k, v, scale, q_prescaled=False):
         round the product back to bf16 before the QK^T MFMA.  Each q_d then carries a relative
         error of up to 2^-8, i.e. a score error of up to 2^-8 scale sum_d |q_d| |k_jd|, which
         adds to delta.  attn_kernel and attn_seqm_kernel scale the fp32 score instead.
+      * q_err / k_err / v_err (optional, shaped like q / k / v): per-element bounds of what the
+        kernel's own q, k, v differ from the reference's by (a fused kernel that projects and
+        rounds them itself).  A score moves by at most
+        scale sum_d (b_q |k| + |q| b_k + b_q b_k), which joins delta (per row, the maximum over
+        the keys); v_j moving by b_v_j moves the result by at most sum_j p_j b_v_j, which joins
+        B.  Without them the bound is what it was.
     The same (1 + 2^-6), + 2^-126 slack as gemm_bound."""
     q, k, v = f64(q), f64(k), f64(v)
     d, nk = q.shape[-1], k.shape[-2]
@@ -144,8 +150,15 @@ def attn_bound(q, k, v, scale, q_prescaled=False):
     ref = p @ v
     smag = scale * (q.abs() @ k.abs().transpose(-1, -2))
     delta = ((d + 2) * E_F32 + (U_BF16 if q_prescaled else 0.0)) * smag.amax(dim=-1, keepdim=True)
+    if q_err is not None or k_err is not None:
+        bq = f64(q_err) if q_err is not None else torch.zeros_like(q)
+        bk = f64(k_err) if k_err is not None else torch.zeros_like(k)
+        s_in = scale * (bq @ k.abs().transpose(-1, -2) + q.abs() @ bk.transpose(-1, -2) + bq @ bk.transpose(-1, -2))
+        delta = delta + s_in.amax(dim=-1, keepdim=True)
     pv = p @ v.abs()
     b = U_BF16 * ref.abs() + (2 * U_BF16 + 2 * torch.expm1(delta) + (nk + 4) * E_F32) * pv
+    if v_err is not None:
+        b = b + p @ f64(v_err)
     return ref, _slack(b)
 
 
@@ -158,6 +171,349 @@ def elem_bound(ref, term_mag, out_dtype):
     if out_dtype == torch.bfloat16:
         b = b + U_BF16 * ref.abs() * SLACK
     return b + TINY
+
+
+# ---------------------------------------------------------------- LayerNorm, row statistics
+def _ln_parts(x, eps):
+    """fp64 row quantities of x (rows, C) and the first-order bounds of layernorm_kernel's
+    (mean, rstd) (ls_norm.hip), shared by ln_bound and row_stats_bound.
+
+      * mean: C - 1 fp32 additions in any order (per-lane chains, then the 16-lane shuffle tree)
+        and one division -- or, in ff_chain_kernel and tattn_fused_kernel, the product with the
+        rounded constant 1.f / C, two roundings: |mean' - mu| <= b_mu = (C + 1) 2^-23 mean|x|.
+      * the second pass sums fl(x - mean')^2.  With delta = mean' - mu, sum (d - delta)^2 =
+        sum d^2 + C delta^2 exactly (sum d = 0), so the mean's error enters the variance only as
+        delta^2; every term carries the subtraction's rounding twice and the product's once,
+        the sum C - 1 additions, then / C (or * (1.f / C): two) and + eps:
+        b_v = (C + 5) 2^-23 (var + eps) + b_mu^2.
+      * rstd = rsqrtf(var' + eps), 1 ulp (v_rsq_f32): b_r = r (b_v / (2 (var + eps)) + 2^-23).
+    """
+    x = f64(x)
+    C = x.shape[-1]
+    mu = x.mean(-1, keepdim=True)
+    d = x - mu
+    var = (d * d).mean(-1, keepdim=True)
+    r = 1.0 / torch.sqrt(var + eps)
+    b_mu = (C + 1) * E_F32 * x.abs().mean(-1, keepdim=True)
+    b_v = (C + 5) * E_F32 * (var + eps) + b_mu * b_mu
+    b_r = r * (0.5 * b_v / (var + eps) + E_F32)
+    return mu, d, r, b_mu, b_r
+
+
+def ln_bound(x, gamma, beta, pe_row, eps, out_dtype):
+    """(ref, B) for y = (x - mu) r gamma + beta (+ pe_row) of layernorm_kernel (ls_norm.hip);
+    x (rows, C) bf16-rounded, gamma / beta (C,) fp32, pe_row None or (rows, C): the pe row each
+    output row must receive.  ref in fp64; with a = (x - mu) r and (b_mu, b_r) of _ln_parts:
+
+        B = u_out |ref| + |gamma| (r b_mu + |x - mu| b_r) + 5 2^-23 (|a gamma| + |beta| + |pe|)
+
+      * r b_mu: the subtracted mean is off by b_mu; |x - mu| b_r: rstd is off by b_r.
+      * 5 2^-23 mag: "(v - mean) * rstd * g + b (+ pe)" is a subtraction, two products and two
+        additions, each within 2^-23 of a partial result no larger than mag (a contraction to
+        fma only removes roundings).
+      * u_out |ref|: the one rounding to bf16 (pack8).
+    (1 + 2^-6) and + 2^-126 as everywhere: the products of two first-order terms."""
+    mu, d, r, b_mu, b_r = _ln_parts(x, eps)
+    g, b = f64(gamma), f64(beta)
+    a = d * r
+    ref = a * g + b
+    mag = (a * g).abs() + b.abs()
+    if pe_row is not None:
+        ref = ref + f64(pe_row)
+        mag = mag + f64(pe_row).abs()
+    bnd = _u_out(out_dtype) * ref.abs() + g.abs() * (r * b_mu + d.abs() * b_r) + 5 * E_F32 * mag
+    return ref, _slack(bnd)
+
+
+def row_stats_bound(x, eps):
+    """(ref, B), both (rows, 2), for the (mean, rstd) pair of ls_row_stats: the statistics branch
+    of layernorm_kernel stores its fp32 mean and rstd as they are, so B = (b_mu, b_r) of
+    _ln_parts with the usual slack."""
+    mu, _, r, b_mu, b_r = _ln_parts(x, eps)
+    return torch.cat([mu, r], -1), _slack(torch.cat([b_mu, b_r], -1))
+
+
+def ln_propagate(a, r, b_x):
+    """First-order effect of a per-element input error b_x on a = (x - mu) r along the last
+    dimension (r (..., 1) = 1 / sqrt(var + eps)): for a kernel that normalises a value it has
+    itself rounded (ff_chain_kernel's h2, xattn's y).
+
+        |da_i| <= r (b_i + mean(b)) + |a_i| r mean(|a| b)
+
+    From da_i = r (dx_i - dmu) + (x_i - mu) dr with |dmu| <= mean(b), and dr = -r^3 dvar / 2,
+    dvar = 2 mean((x - mu)(dx - dmu)) = 2 mean((x - mu) dx) (the dmu part vanishes: mean(x - mu)
+    = 0), so |dr| <= r^2 mean(|a| b) and |(x_i - mu) dr| = |a_i| r mean(|a| b).  Second-order
+    terms (b^2) are left to the SLACK factor of the bound this feeds."""
+    a, r, b_x = f64(a), f64(r), f64(b_x)
+    return r * (b_x + b_x.mean(-1, keepdim=True)) + a.abs() * r * (a.abs() * b_x).mean(-1, keepdim=True)
+
+
+# ---------------------------------------------------------------- GroupNorm statistics
+def _gn_ref(mean, var, eps, gamma, beta, cpg):
+    """fp64 (scale, shift) (S, C) from per-(sample, group) mean / var (S, G)."""
+    r = 1.0 / torch.sqrt(var + eps)
+    C = mean.shape[1] * cpg
+    g = f64(gamma) if gamma is not None else torch.ones(C, dtype=torch.float64)
+    b = f64(beta) if beta is not None else torch.zeros(C, dtype=torch.float64)
+    rc, mc = r.repeat_interleave(cpg, 1), mean.repeat_interleave(cpg, 1)
+    scale = g * rc
+    return scale, b - mc * scale, r, rc, mc, g, b
+
+
+def _gn_affine_bound(b_mean, b_r, r, rc, mc, g, b, scale, cpg):
+    """The tail both GroupNorm finalisers share: sc = gamma * rstd' (one fp32 product) and
+    shift = beta - mean' * sc (a product and a subtraction), mean' and rstd' fp32:
+        b_sc = |gamma| b_r + 2^-23 |sc|
+        b_sh = |sc| b_mean + |mean| b_sc + 2^-23 |mean sc| + 2^-23 (|beta| + |mean sc|)"""
+    b_rc, b_mc = b_r.repeat_interleave(cpg, 1), b_mean.repeat_interleave(cpg, 1)
+    b_sc = g.abs() * b_rc + E_F32 * scale.abs()
+    ms = (mc * scale).abs()
+    b_sh = scale.abs() * b_mc + mc.abs() * b_sc + E_F32 * ms + E_F32 * (b.abs() + ms)
+    return _slack(b_sc), _slack(b_sh)
+
+
+def gn_stats_bound(x, groups, eps, gamma, beta, nsplit, R):
+    """((scale, shift) fp64, (B_scale, B_shift)), each (S, C), for gn_stats_kernel (ls_norm.hip);
+    x (S, pps, C) bf16-rounded (a concat already joined), nsplit and R as ls_groupnorm computes
+    them (gn_nsplit; R = 256 / (C / 8) rows of threads, 1 from C / 8 > 256).
+
+    The kernel shifts by k_g = x[s, 0, g cpg] and sums d = x - k_g and d^2 per thread in fp32,
+    a thread taking every R-th row of its split: n_t = ceil(ceil(pps / nsplit) / R) terms.
+    Everything after the per-thread sums is fp64 (2^-53: left to the slack).
+      * S1: each d carries the subtraction's rounding, the chain n_t - 1 additions:
+        |S1' - S1| <= n_t 2^-23 sum |d|, so b_m1 = n_t 2^-23 mean|d| on m1 = S1 / n.
+      * S2: fl(d)^2 carries two subtraction roundings and the product's, the chain n_t - 1:
+        |S2' - S2| <= (n_t + 2) 2^-23 sum d^2.
+      * var = S2 / n - m1^2: b_var = (n_t + 2) 2^-23 S2 / n + 2 |m1| b_m1 + b_m1^2 (the
+        cancellation the shift leaves is paid through S2 / n = var + m1^2).
+      * mean' = (float)(k_g + m1): b_mean = b_m1 + 2^-24 |mean|;
+        rstd' = (float)(1 / sqrt(var + eps)): b_r = r (b_var / (2 (var + eps)) + 2^-24).
+      * then _gn_affine_bound."""
+    x = f64(x)
+    S, pps, C = x.shape
+    cpg = C // groups
+    xg = x.reshape(S, pps, groups, cpg)
+    mean = xg.mean((1, 3))
+    var = ((xg - mean[:, None, :, None]) ** 2).mean((1, 3))
+    scale, shift, r, rc, mc, g, b = _gn_ref(mean, var, eps, gamma, beta, cpg)
+    n_t = -(-(-(-pps // nsplit)) // R)
+    d = xg - xg[:, :1, :, :1]
+    m1 = d.mean((1, 3))
+    b_m1 = n_t * E_F32 * d.abs().mean((1, 3))
+    b_var = (n_t + 2) * E_F32 * (d * d).mean((1, 3)) + 2 * m1.abs() * b_m1 + b_m1 * b_m1
+    b_mean = b_m1 + U_F32 * mean.abs()
+    b_r = r * (0.5 * b_var / (var + eps) + U_F32)
+    return (scale, shift), _gn_affine_bound(b_mean, b_r, r, rc, mc, g, b, scale, cpg)
+
+
+def gn_colsum_bound(cs, slots_per_sample, groups, eps, gamma, beta, slot_rows=128):
+    """((scale, shift) fp64, (B_scale, B_shift)) for gn_colsum_finalize_kernel; cs (slots, 2, C)
+    the given fp32 column sums (a concat already joined along C).  The reference is fp64 on
+    those very sums, so what remains is the kernel's fp64 tree (each of the slots cpg terms
+    within 2^-52 of sum |terms| whatever the order; var = s2 / n - mean^2 cancels in fp64:
+    2^-52 (s2 / n + mean^2) counted once more), the casts (float)mean and (float)rstd
+    (2^-24 each), and _gn_affine_bound."""
+    cs = f64(cs)
+    C = cs.shape[-1]
+    cpg = C // groups
+    S = cs.shape[0] // slots_per_sample
+    n = float(slots_per_sample * slot_rows * cpg)
+    t = cs.reshape(S, slots_per_sample, 2, groups, cpg)
+    s1, s2 = t[:, :, 0].sum((1, 3)), t[:, :, 1].sum((1, 3))
+    a1, a2 = t[:, :, 0].abs().sum((1, 3)), t[:, :, 1].abs().sum((1, 3))
+    mean = s1 / n
+    var = (s2 / n - mean * mean).clamp_min(0.0)
+    scale, shift, r, rc, mc, g, b = _gn_ref(mean, var, eps, gamma, beta, cpg)
+    nt = slots_per_sample * cpg
+    e64 = 2.0 ** -52
+    b_mean64 = nt * e64 * a1 / n
+    b_var = nt * e64 * a2 / n + 2 * mean.abs() * b_mean64 + e64 * (a2 / n + mean * mean)
+    b_mean = b_mean64 + U_F32 * mean.abs()
+    b_r = r * (0.5 * b_var / (var + eps) + U_F32)
+    return (scale, shift), _gn_affine_bound(b_mean, b_r, r, rc, mc, g, b, scale, cpg)
+
+
+def colsum_bound(y, slot_rows=128):
+    """(ref, B), each (M / 128, 2, N), for ls_gn_colsum (colsum_pass_kernel, ls_gemm.hip): per
+    128-row slot the column sums of y and of y^2.  y is bf16, so y^2 is exact in fp32 (and the
+    kernel's fma adds it unrounded); what rounds is the additions: 8 chains of 16 rows and the
+    8-way merge, fewer than 128 in all, any order: B = 128 2^-23 sum |terms|."""
+    y = f64(y)
+    M, N = y.shape
+    t = y.reshape(M // slot_rows, slot_rows, N)
+    ref = torch.stack([t.sum(1), (t * t).sum(1)], 1)
+    mag = torch.stack([t.abs().sum(1), (t * t).sum(1)], 1)
+    return ref, _slack(slot_rows * E_F32 * mag)
+
+
+def gn_apply_bound(x, scale, shift, silu_on):
+    """(ref, B) for y = act(x scale + shift) of gn_apply_kernel / gn_apply_u_kernel; x (S, pps, C)
+    bf16-rounded, scale / shift (S, C) the fp32 values handed to the kernel.  The affine is one
+    fmaf (2 2^-23 (|x scale| + |shift|) covers the unfused form too), then act_bound's SiLU
+    term or, without it, the bf16 rounding alone."""
+    x, sc, sh = f64(x), f64(scale)[:, None, :], f64(shift)[:, None, :]
+    pre = x * sc + sh
+    b_pre = 2 * E_F32 * ((x * sc).abs() + sh.abs())
+    if silu_on:
+        return act_bound("silu", pre, b_pre, torch.bfloat16)
+    return pre, _slack(b_pre + U_BF16 * pre.abs())
+
+
+# ---------------------------------------------------------------- composing a fused kernel's bound
+def chain_linear(b_gemm, w, b_in):
+    """A linear stage out = in w^T whose input is itself only known to b_in (rows, K): the
+    stage's own gemm_bound b_gemm (rows, N) plus sum_k |w_nk| b_in_k."""
+    return f64(b_gemm) + f64(b_in) @ f64(w).abs().transpose(-1, -2)
+
+
+def chain_round(b, value):
+    """An intermediate the kernel rounds to bf16 (and the reference does not): + 2^-8 |value|."""
+    return f64(b) + U_BF16 * f64(value).abs()
+
+
+def ln_from_stats_bound(x, stats):
+    """(a, B) for the in-register LayerNorm of ff_fused_kernel / xattn_fused_kernel (ls_ff.hip
+    "v[e] = (__bf16)fmaf((float)v[e], rstd, nmr)" with "nmr = -mr.x * mr.y"; the same two lines
+    in ls_xattn.hip): a = (x - mean) rstd in fp64 from the GIVEN fp32 (mean, rstd) rows, one
+    rounded product nmr, one fma, one rounding to bf16:
+        B = 2^-8 |a| + 2 2^-23 (|x rstd| + |mean rstd|)"""
+    x, st = f64(x), f64(stats)
+    m, r = st[:, :1], st[:, 1:2]
+    a = (x - m) * r
+    return a, _slack(U_BF16 * a.abs() + 2 * E_F32 * ((x * r).abs() + (m * r).abs()))
+
+
+def _linear(a, w, bias=None, res=None):
+    """(value, magnitude) of a w^T (+ bias) (+ res) in fp64."""
+    a, w = f64(a), f64(w)
+    v, m = a @ w.T, a.abs() @ w.abs().T
+    for t in (bias, res):
+        if t is not None:
+            v, m = v + f64(t), m + f64(t).abs()
+    return v, m
+
+
+def _geglu_ff(a, b_a, w1g, b1, b1_mag, w2):
+    """The FeedForward body both fused kernels share (ff_fused_kernel's chunk loop, reused by
+    ff_chain_kernel's phase B): pre = W1 a + b1 in fp32 (C accumulations; a known to b_a; the
+    host folded b1 = b + W beta in fp32: (C + 2) 2^-23 b1_mag), G = h gelu(g) rounded to bf16
+    ("gv[r] = (__bf16)((acc[0][r] + hb0[r]) * gelu_erf(acc[1][r] + gb0[r]))"): geglu_bound.
+    Returns (G, b_G, W2 G, its magnitude, the bound chain_linear(., W2, b_G) adds)."""
+    W1 = f64(w1g)
+    inner, C = W1.shape[0] // 2, W1.shape[1]
+    pre, mag = _linear(a, W1, b1)
+    b_pre = chain_linear(gemm_bound(pre, mag, C, None), W1, b_a) + (C + 2) * E_F32 * f64(b1_mag)
+    G, b_G = geglu_bound(pre[:, :inner], b_pre[:, :inner], pre[:, inner:], b_pre[:, inner:], torch.bfloat16)
+    return G, b_G
+
+
+def ff_bound(x, stats, w1g, b1, b1_mag, w2, b2):
+    """(ref, B) for y = x + W2 GEGLU(W1 LN(x) + b1) + b2 of ff_fused_kernel, composed stage by
+    stage: ln_from_stats_bound -> _geglu_ff -> the second GEMM (inner accumulations, + b2 + x,
+    one rounding to bf16) with chain_linear for G's own bound.  w1g (2 inner, C) = [h; g] rows
+    with gamma folded and rounded to bf16 once, b1 its fp64 bias b + W beta with b1_mag =
+    |b| + |W| |beta|; w2 (C, inner) bf16-rounded."""
+    a, b_a = ln_from_stats_bound(x, stats)
+    G, b_G = _geglu_ff(a, b_a, w1g, b1, b1_mag, w2)
+    y, mag = _linear(G, w2, b2, x)
+    return y, chain_linear(gemm_bound(y, mag, G.shape[1], torch.bfloat16), w2, b_G)
+
+
+def ff_chain_bound(o, h1, xb, wo, bo, w1g, b1, b1_mag, w2, b2, wp, bp, eps):
+    """(ref z, B) for ff_chain_kernel (ls_ff.hip), the kernel's intermediate roundings in order:
+      1. h2 = o Wo^T + bo + h1 rounded to bf16 (phase A: "init_cols(a.bo); proj(0);" then
+         "pk0 = pack2(out[f][t][0] + ...)": C accumulations, bias, residual): gemm_bound(bf16).
+      2. LayerNorm of that rounded h2 with the kernel's own fp32 statistics ("mean =
+         xor16_32_sum(s1) * (1.0f / C)", "rstd = rsqrtf(...)"), rounded to bf16
+         (acc_to_operand: "v[e] = (__bf16)((out[f][2 * s + (e >> 2)][e & 3] - mean) * rstd)"):
+         ln_propagate of b_h2, the statistics' own error r b_mu + |h2 - mu| b_r (_ln_parts),
+         and (2^-8 + 3 2^-23) |a| for the subtraction, the product and the rounding.
+      3. the FeedForward body (_geglu_ff); its accumulators start at h2 + b2 ("out[f][t][0] +=
+         b.x"), so y = h2 + W2 G + b2 carries b_h2 one to one, and is rounded to bf16 as phase
+         C's operand ("acc_to_operand(f, 0.f, 1.f)").
+      4. z = y Wp^T + bp + xb rounded to bf16 (phase C and the epilogue's pack2)."""
+    C = f64(wo).shape[0]
+    h2, mag = _linear(o, wo, bo, h1)
+    b_h2 = gemm_bound(h2, mag, C, torch.bfloat16)
+    mu, d, r, b_mu, b_r = _ln_parts(h2, eps)
+    a = d * r
+    b_a = _slack(ln_propagate(a, r, b_h2) + r * b_mu + d.abs() * b_r + (U_BF16 + 3 * E_F32) * a.abs())
+    G, b_G = _geglu_ff(a, b_a, w1g, b1, b1_mag, w2)
+    y, mag = _linear(G, w2, b2, h2)
+    b_y = chain_linear(gemm_bound(y, mag, G.shape[1], torch.bfloat16), w2, b_G) + b_h2
+    z, mag = _linear(y, wp, bp, xb)
+    return z, chain_linear(gemm_bound(z, mag, C, torch.bfloat16), wp, b_y)
+
+
+def stored_row_stats_bound(y, eps, chain=8):
+    """(ref, B), each (rows, 2), for (mean, rstd) of the STORED bf16 rows y as a GEMM epilogue
+    emits them (xattn_fused_kernel: "c1 += (b0 + b1) + (b2 + b3)", "c2 = fmaf(b0, b0, ...)" per
+    32-column chunk, then double): fp32 chains of `chain` terms (8 2^-23 of sum |y|, of sum y^2),
+    fp64 from there on, var = S2 / C - mean^2 paying 2 |mean| b_mean, the casts 2^-24."""
+    y = f64(y)
+    mu = y.mean(-1, keepdim=True)
+    m2 = (y * y).mean(-1, keepdim=True)
+    var = (m2 - mu * mu).clamp_min(0.0)
+    r = 1.0 / torch.sqrt(var + eps)
+    b_m = chain * E_F32 * y.abs().mean(-1, keepdim=True)
+    b_var = chain * E_F32 * m2 + 2 * mu.abs() * b_m
+    return torch.cat([mu, r], -1), _slack(torch.cat([b_m + U_F32 * mu.abs(), r * (0.5 * b_var / (var + eps) + U_F32)], -1))
+
+
+def _heads(t, n, rows, heads):
+    """(n rows, heads d) -> (n, heads, rows, d)."""
+    return t.reshape(n, rows, heads, -1).permute(0, 2, 1, 3)
+
+
+def xattn_bound(x, stats, wq, bq, bq_mag, kv, L, hw, wo, bo, heads=8):
+    """(ref y, B) for xattn_fused_kernel (ls_xattn.hip), stage by stage:
+      1. a = LN(x) from the given statistics, bf16: ln_from_stats_bound.
+      2. q' = Wq a + bq in log2 units (wq = W gamma log2(e) / sqrt(d) rounded to bf16 once, as
+         packing.pack_xattn_q / ops.pack_cross_attention do; bq its fp64 bias, folded in fp32 on
+         the host: (C + 2) 2^-23 bq_mag), rounded to bf16 ("qk0[r] = (__bf16)(qa[0][r] + bq[0])").
+      3. softmax(ln 2 q' k^T) v over the image's L keys: attn_bound with q_err = b_q (P rounded to
+         bf16, the row sum of the rounded P, o / l rounded to bf16: "ofr[ja][r] = (__bf16)(o[0][r] *
+         inv)" -- attn_bound's three 2^-8 terms).
+      4. y = x + Wo o + bo, C accumulations (the padded k-slots add exact zeros), bf16."""
+    x = f64(x)
+    M, C = x.shape
+    n_img = M // hw
+    a, b_a = ln_from_stats_bound(x, stats)
+    q, mag = _linear(a, wq, bq)
+    b_q = chain_round(chain_linear(gemm_bound(q, mag, C, None), wq, b_a) + (C + 2) * E_F32 * f64(bq_mag), q)
+    kv = f64(kv)
+    k, v = _heads(kv[:, :C], n_img, L, heads), _heads(kv[:, C:2 * C], n_img, L, heads)
+    o, b_o = attn_bound(_heads(q, n_img, hw, heads), k, v, math.log(2.0), q_err=_heads(b_q, n_img, hw, heads))
+    o, b_o = (t.permute(0, 2, 1, 3).reshape(M, C) for t in (o, b_o))
+    y, mag = _linear(o, wo, bo, x)
+    return y, chain_linear(gemm_bound(y, mag, C, torch.bfloat16), wo, b_o)
+
+
+def tattn_bound(x, gamma, bpe, wq_packed, wk, wv, n_samples, F, S, heads, eps):
+    """(ref o, B) for tattn_fused_kernel (ls_motion.hip); x rows "(b f) s".
+      1. LayerNorm with the kernel's own fp32 statistics, + (beta + pe[f]), bf16
+         ("v[e] = (__bf16)fmaf(((float)v[e] - mean[i]) * rstd[i], g8[e], b8[e])"): ln_bound.
+      2. q', k, v = W ln (C accumulations), each rounded to bf16 ("pack4(acc[i][j], 1.f)"):
+         gemm_bound + chain_linear + chain_round.  wq_packed is wq log2(e) / sqrt(d) rounded to
+         bf16 as ops.pack_temporal stores it; the reference divides the pre-scale out again in
+         fp64 and takes the softmax at scale 1 / sqrt(d).
+      3. softmax over the F frames of a pixel and P V: attn_bound with q_err, k_err, v_err."""
+    x = f64(x)
+    C = x.shape[1]
+    d = C // heads
+    sc = math.log2(math.e) / math.sqrt(d)
+    frame = (torch.arange(x.shape[0]) // S) % F
+    ln, b_ln = ln_bound(x, gamma, torch.zeros(C), f64(bpe)[frame], eps, torch.bfloat16)
+    out = []
+    for w in (f64(wq_packed) / sc, wk, wv):
+        p, mag = _linear(ln, w)
+        b_p = chain_round(chain_linear(gemm_bound(p, mag, C, None), w, b_ln), p)
+        # rows (b f) s -> (b, s, head, f, d)
+        out += [t.reshape(n_samples, F, S, heads, d).permute(0, 2, 3, 1, 4) for t in (p, b_p)]
+    q, b_q, k, b_k, v, b_v = out
+    o, b_o = attn_bound(q, k, v, 1.0 / math.sqrt(d), q_err=b_q, k_err=b_k, v_err=b_v)
+    back = lambda t: t.permute(0, 3, 1, 2, 4).reshape(n_samples * F * S, C)
+    return back(o), back(b_o)
 
 
 def assert_elementwise(got, ref, bound, where=None, name="output"):
@@ -320,3 +676,232 @@ def needle_qkv(batch, heads, nq, nk, d, seed):
         kj = k[:, :, j]
         q[:, :, i] = 8.0 * math.sqrt(d) * kj / (kj * kj).sum(-1, keepdim=True)
     return bf16_round(q), k, bf16_round(v)
+
+
+# ---------------------------------------------------------------- norm cases (tests/test_gpu_edges_norm.py)
+LN_C = (8, 136, 320, 520, 1024, 1280, 1536, 1664, 2048)  # layernorm_kernel<NCH>: 1, 2, 3, 5, 8, 10, 12, 16, 16
+LN_ROWS = (1, 15, 17, 33)
+LN_PE_RPF, LN_PE_FRAMES = 3, 4  # the frame index wraps inside 33 rows
+LN_EPS = 1e-5
+
+
+def ln_case(rows, C, mean_sigmas, seed=0):
+    """bf16-rounded x (rows, C) with row standard deviations 0.5 .. 2 and row means of
+    mean_sigmas standard deviations; fp32 gamma, beta (C,), pe (LN_PE_FRAMES, C)."""
+    g = torch.Generator().manual_seed(1000 * seed + 7 * C + rows)
+    sig = 0.5 + 1.5 * torch.rand(rows, 1, generator=g)
+    x = bf16_round(sig * (torch.randn(rows, C, generator=g) + mean_sigmas))
+    gamma = 1.0 + 0.3 * torch.randn(C, generator=g)
+    beta = 0.2 * torch.randn(C, generator=g)
+    pe = 0.5 * torch.randn(LN_PE_FRAMES, C, generator=g)
+    return x, gamma, beta, pe
+
+
+def ln_pe_rows(pe, rows, rpf=LN_PE_RPF, frames=LN_PE_FRAMES):
+    """The pe row every output row receives: pe[(row // rpf) % frames]."""
+    return pe[(torch.arange(rows) // rpf) % frames]
+
+
+GN_THREADS = 256
+
+
+def gn_R(C):
+    """Pixel rows of threads per block of gn_stats_kernel (ls_norm.hip, "if (CC <= GN_THREADS)
+    { R = GN_THREADS / CC; ..." and the same two lines in gn_nsplit / ls_groupnorm)."""
+    CC = C // 8
+    return GN_THREADS // CC if CC <= GN_THREADS else 1
+
+
+def gn_nsplit(n_samples, pps, C):
+    """gn_nsplit of ls_norm.hip: min(ceil(512 / n_samples), pps / (8 R)), clamped to [1, 4096]."""
+    ns = min(-(-512 // n_samples), pps // (8 * gn_R(C)))
+    return max(1, min(ns, 4096))
+
+
+def _gn_cases():
+    out = []
+    for C in (32, 96, 320):  # 32 groups; C = 96: cpg 3, groups straddle the 16-byte chunks
+        for pps in (1, 7, 8 * gn_R(C) + 1, 4096):
+            out.append((f"c{C}_p{pps}", C, 0, 32, 3, pps))
+    for pps in (1, 7, 9):  # C / 8 = 320 > 256 threads: the nchunk > 1 branch, R = 1
+        out.append((f"c2560_p{pps}", 2560, 0, 32, 3, pps))
+    out.append(("c2560_p4096_one", 2560, 0, 32, 1, 4096))  # 512 splits on one accumulator and ticket
+    for pps in (1, 7, 8 * gn_R(128) + 1, 4096):  # 64 groups: the L = 4 branch
+        out.append((f"c128g64_p{pps}", 128, 0, 64, 3, pps))
+    for pps in (1, 7, 8 * gn_R(160) + 1, 4096):  # concat: group 19 (channels 95 .. 99) straddles x1 | x2
+        out.append((f"cat96+64_p{pps}", 96, 64, 32, 3, pps))
+    out.append(("c32_520x4", 32, 0, 32, 520, 4))  # nsplit 1, many samples
+    out.append(("c32_p4096_one", 32, 0, 32, 1, 4096))
+    out.append(("c320_p4096_one", 320, 0, 32, 1, 4096))
+    return tuple(out)
+
+
+GN_CASES = _gn_cases()  # (name, C1, C2, groups, n_samples, pps)
+GN_MEANS = (0, 10, 30)  # mean / std
+GN_EPS = 1e-5
+
+
+def gn_case(C1, C2, n_samples, pps, mean_sigmas, seed=0):
+    """bf16-rounded x (n_samples, pps, C1 + C2), unit standard deviation, sample s at a mean of
+    mean_sigmas (1 + s / 8), and the x2 half of a concat a further 5 higher (so the group that
+    straddles the boundary sees both levels); fp32 gamma, beta."""
+    C = C1 + C2
+    g = torch.Generator().manual_seed(1000 * seed + 13 * C + pps + n_samples)
+    x = torch.randn(n_samples, pps, C, generator=g)
+    x = x + mean_sigmas * (1.0 + torch.arange(n_samples).reshape(-1, 1, 1) / 8.0)
+    if C2:
+        x[:, :, C1:] += 5.0
+    gamma = 1.0 + 0.3 * torch.randn(C, generator=g)
+    beta = 0.2 * torch.randn(C, generator=g)
+    return bf16_round(x), gamma, beta
+
+
+# ls_groupnorm_colsum on synthetic column sums: (cpg, slots per sample, C1, C2 or None = the rest),
+# 32 groups, 3 samples; the concat boundary C1 falls inside a group wherever cpg > 1
+_GN_COLSUM_C1 = {1: 24, 3: 64, 5: 96, 40: 768}
+GN_COLSUM_CASES = tuple((cpg, slots, C1, C2) for cpg in (1, 3, 5, 40) for slots in (1, 3)
+                        for C1, C2 in ((32 * cpg, 0), (_GN_COLSUM_C1[cpg], None)))
+
+
+def gn_colsum_case(cpg, slots, C1, C2, seed=0):
+    """fp32 column sums cs1 (3 slots, 2, C1), cs2 (3 slots, 2, C2) or None, as a producer would
+    emit them for data of mean 2 and unit deviation; gamma, beta."""
+    C = 32 * cpg
+    C2 = C - C1 if C2 is None else C2
+    g = torch.Generator().manual_seed(1000 * seed + 17 * cpg + slots + C1)
+    y = bf16_round(torch.randn(3 * slots * 128, C, generator=g) + 2.0).reshape(3 * slots, 128, C)
+    cs = torch.stack([y.sum(1), (y * y).sum(1)], 1)  # fp32 sums: the kernel's input as it is
+    gamma = 1.0 + 0.3 * torch.randn(C, generator=g)
+    beta = 0.2 * torch.randn(C, generator=g)
+    cs1 = cs[:, :, :C1].contiguous()
+    cs2 = cs[:, :, C1:].contiguous() if C2 else None
+    return cs1, cs2, gamma, beta
+
+
+# ls_groupnorm_apply: (name, C1, C2, n_samples, pps).  ppb = 256 / (C / 8) pixels per block pass;
+# gn_apply_u_kernel (4 ppb pixels per block) needs ppb >= 2 and 4 ppb <= pps, else gn_apply_kernel
+GN_APPLY_CASES = (
+    ("u_c128_88x3", 128, 0, 3, 88),       # ppb 16: 264 = 4 * 64 + 8, lanes pl >= 8 of the last block have no pixel;
+                                          # 88 = 64 + 24: a sample boundary inside the second block's range
+    ("u_c96_64x3", 96, 0, 3, 64),         # CC 12, ppb 21: 252 live threads of 256, blocks of 84 pixels over samples of 64
+    ("stride_c96_9x5", 96, 0, 5, 9),      # 4 ppb = 84 > pps: the grid-stride kernel, a sample boundary in every pass
+    ("stride_c1280_5x3", 1280, 0, 3, 5),  # ppb 1, 160 live lanes of 192: the grid-stride kernel
+    ("u_cat96+64_50x3", 96, 64, 3, 50),   # concat, ppb 12, blocks of 48 pixels over samples of 50
+    ("stride_cat64+32_9x5", 64, 32, 5, 9),
+)
+
+
+# ---------------------------------------------------------------- fused transformer-block cases
+# (tests/test_gpu_edges_ff.py, tests/test_gpu_edges_fused_attn.py)
+#
+# A composed bound is a worst case: every stage adds sum_k |w_k| b_k, which for dense Gaussian
+# weights is about 0.64 sqrt(K) times what the same errors add up to with random signs -- at
+# K = 320 / 1280 the bound would be ten to twenty bf16 steps wide and a dropped column would fit
+# inside it.  The weights here are therefore a weak dense background (deviation 2^-6 / sqrt(K):
+# every packed position still carries a distinct value) under `nnz` strong entries per row
+# (deviation 1 / sqrt(nnz)) at random columns, so |sum w a| is within a small factor of
+# sum |w a| and the bound stays a few bf16 steps wide.
+FF_C, FF_INNER = 320, 1280
+FF_M = (1, 127, 129, 300)
+FF_CHAIN_M = (128, 384)
+FF_W2_NEEDLES = (0, 3, 4, 15, 16, 31, 32, 1279)  # inner columns of W2 scaled by 8
+FF_W1_NEEDLES = (0, 31, 32, 319)                 # k-columns of W1 scaled by 8
+LOG2E = math.log2(math.e)
+
+
+def sparse_weight(n, k, nnz, seed, bg=2.0 ** -6):
+    g = torch.Generator().manual_seed(seed)
+    w = torch.randn(n, k, generator=g) * (bg / math.sqrt(k))
+    idx = torch.rand(n, k, generator=g).argsort(1)[:, :nnz]
+    return w.scatter_(1, idx, torch.randn(n, nnz, generator=g) / math.sqrt(nnz))
+
+
+def host_row_stats(x, eps=1e-5):
+    """fp32 (mean, rstd) rows as a producer would hand them over (the kernels take them as they are)."""
+    x = f64(x)
+    mu = x.mean(-1, keepdim=True)
+    var = ((x - mu) ** 2).mean(-1, keepdim=True)
+    return torch.cat([mu, 1.0 / torch.sqrt(var + eps)], -1).float()
+
+
+def _ff_weights(seed):
+    """Logical FeedForward tensors: gamma, beta, w1 (2 inner, C) = [h; g], b1, w2 (C, inner), b2,
+    and what the reference uses: w1g = w1 gamma rounded to bf16 once (unet._Dev.packed_ln), b1f =
+    b1 + w1 beta in fp64 with its magnitude, w2 rounded to bf16."""
+    g = torch.Generator().manual_seed(seed)
+    C, inner = FF_C, FF_INNER
+    gamma, beta = 1.0 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    w1 = sparse_weight(2 * inner, C, 8, seed + 1)
+    w1[:, list(FF_W1_NEEDLES)] *= 8.0
+    b1 = 0.1 * torch.randn(2 * inner, generator=g)
+    w2 = sparse_weight(C, inner, 16, seed + 2)
+    w2[:, list(FF_W2_NEEDLES)] *= 8.0
+    b2 = 0.1 * torch.randn(C, generator=g)
+    return dict(gamma=gamma, beta=beta, w1=w1, b1=b1, w2=w2, b2=b2,
+                w1g=bf16_round(w1 * gamma[None, :]), b1f=f64(b1) + f64(w1) @ f64(beta),
+                b1_mag=f64(b1).abs() + f64(w1).abs() @ f64(beta).abs(), w2r=bf16_round(w2))
+
+
+def ff_case(M, seed=0):
+    """ls_feedforward inputs: x (M, C) bf16-rounded, its fp32 row statistics, _ff_weights."""
+    g = torch.Generator().manual_seed(100 * seed + M)
+    x = bf16_round(4.0 * torch.randn(M, FF_C, generator=g) + 0.5)
+    return dict(x=x, stats=host_row_stats(x), **_ff_weights(40 + seed))
+
+
+def ff_chain_case(M, seed=0):
+    """ls_ff_chain inputs: o, h1, xb (M, C), to_out (wo, bo), the FeedForward, proj_out (wp, bp)."""
+    g = torch.Generator().manual_seed(200 * seed + M)
+    r = lambda *s: torch.randn(*s, generator=g)
+    C = FF_C
+    out = dict(o=bf16_round(r(M, C)), h1=bf16_round(4.0 * r(M, C) + 0.5), xb=bf16_round(4.0 * r(M, C)),
+               wo=sparse_weight(C, C, 8, seed + 61), bo=0.1 * r(C), wp=sparse_weight(C, C, 8, seed + 62), bp=0.1 * r(C),
+               **_ff_weights(50 + seed))
+    out["wor"], out["wpr"] = bf16_round(out["wo"]), bf16_round(out["wp"])
+    return out
+
+
+XA_HW, XA_IMGS = 128, 3
+XA_L = (1, 7, 50, 64)
+XA_NEEDLE_KEYS = (0, 15, 16, 31, 32)  # and L - 1: V rows scaled by 16
+
+
+def xattn_case(L, seed=0):
+    """ls_cross_attention_block inputs: x (3 * 128, 320), its statistics, to_q (C, C) with norm2's
+    gamma / beta, kv (3 L, 2 C) = k | v with small keys (scores within a fraction of a log2 unit:
+    the bound's score term stays small) and the V rows of the needle keys scaled by 16, to_out."""
+    C, heads = 320, 8
+    M = XA_IMGS * XA_HW
+    g = torch.Generator().manual_seed(300 * seed + L)
+    r = lambda *s: torch.randn(*s, generator=g)
+    x = bf16_round(4.0 * r(M, C) + 0.5)
+    gamma, beta = 1.0 + 0.2 * r(C), 0.1 * r(C)
+    wq, wo, bo = sparse_weight(C, C, 8, seed + 71), sparse_weight(C, C, 8, seed + 72), 0.1 * r(C)
+    kv = torch.cat([0.25 * r(XA_IMGS * L, C), r(XA_IMGS * L, C)], 1)
+    for j in sorted({j for j in XA_NEEDLE_KEYS + (L - 1,) if j < L}):
+        kv[j::L, C:] *= 16.0
+    sc = LOG2E / math.sqrt(C // heads)
+    return dict(x=x, stats=host_row_stats(x), gamma=gamma, beta=beta, wq=wq, wo=wo, bo=bo, kv=bf16_round(kv),
+                wqr=bf16_round((wq * gamma[None, :]) * sc), bqf=(f64(wq) @ f64(beta)) * sc,
+                bq_mag=(f64(wq).abs() @ f64(beta).abs()) * sc, wor=bf16_round(wo))
+
+
+TA_CASES = ((320, 16), (640, 8))  # (C, S): two blocks per sample each
+TA_F = (1, 5, 7, 16)
+TA_SAMPLES = 2
+
+
+def tattn_case(C, S, F, seed=0):
+    """ls_temporal_attention inputs: x rows "(b f) s" (2 F S, C), LayerNorm gamma / beta, pe (24, C),
+    the logical wq, wk (small, as xattn_case's keys), wv, and wqp = wq log2(e) / sqrt(d) rounded to
+    bf16 as ops.pack_temporal stores it, wkr, wvr."""
+    heads = 8
+    g = torch.Generator().manual_seed(400 * seed + C + F)
+    r = lambda *s: torch.randn(*s, generator=g)
+    x = bf16_round(2.0 * r(TA_SAMPLES * F * S, C) + 0.5)
+    gamma, beta, pe = 1.0 + 0.2 * r(C), 0.1 * r(C), 0.5 * r(24, C)
+    wq, wk, wv = sparse_weight(C, C, 8, seed + 81), 0.25 * sparse_weight(C, C, 8, seed + 82), sparse_weight(C, C, 8, seed + 83)
+    sc = LOG2E / math.sqrt(C // heads)
+    bpe = beta.reshape(1, C).repeat(16, 1) + pe[:16]
+    return dict(x=x, gamma=gamma, beta=beta, pe=pe, bpe=bpe, wq=wq, wk=wk, wv=wv, wqp=bf16_round(wq * sc),
+                wkr=bf16_round(wk), wvr=bf16_round(wv))

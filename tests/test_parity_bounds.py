@@ -257,3 +257,548 @@ def test_assert_unchanged():
     x.view(torch.int16)[3, 4] ^= 1  # one bit
     with pytest.raises(AssertionError, match="changed"):
         P.assert_unchanged(x, snap)
+
+
+# ---------------------------------------------------------------- LayerNorm / row statistics
+def emulate_ln(x, gamma, beta, pe_row, eps, order="lanes", truncate=False, stats_only=False):
+    """layernorm_kernel in fp32: "lanes" sums as the kernel does (lane sub owns chunks sub + 16 q
+    of 8 channels, then a 16-lane xor tree), "pairwise" is torch's own fp32 sum."""
+    rows, C = x.shape
+
+    def rsum(v):
+        if order == "pairwise":
+            return v.sum(-1, keepdim=True)
+        CC = C // 8
+        pad = torch.zeros(rows, (-CC) % 16 * 8)
+        t = torch.cat([v, pad], 1).reshape(rows, -1, 16, 8)  # (q, lane, j)
+        acc = torch.zeros(rows, 16)
+        for q in range(t.shape[1]):
+            for j in range(8):
+                acc = acc + t[:, q, :, j]
+        for o in (8, 4, 2, 1):
+            acc = acc + acc[:, torch.arange(16) ^ o]
+        return acc[:, :1]
+
+    mean = rsum(x) / C
+    d = x - mean
+    rstd = torch.rsqrt(rsum(d * d) / C + eps)
+    if stats_only:
+        return torch.cat([mean, rstd], 1)
+    o = d * rstd * gamma + beta
+    if pe_row is not None:
+        o = o + pe_row
+    if truncate:
+        return (o.view(torch.int32) & -65536).view(torch.float32)
+    return o.to(torch.bfloat16).float()
+
+
+@pytest.mark.parametrize("C", P.LN_C)
+@pytest.mark.parametrize("mean_sigmas", [0, 30])
+@pytest.mark.parametrize("order", ["lanes", "pairwise"])
+def test_layernorm_emulation_passes(C, mean_sigmas, order):
+    for rows in P.LN_ROWS:
+        x, gamma, beta, pe = P.ln_case(rows, C, mean_sigmas)
+        for pe_row in (None, P.ln_pe_rows(pe, rows)):
+            ref, bound = P.ln_bound(x, gamma, beta, pe_row, P.LN_EPS, torch.bfloat16)
+            worst = P.assert_elementwise(emulate_ln(x, gamma, beta, pe_row, P.LN_EPS, order), ref, bound)
+            P.assert_elementwise(ref.to(torch.bfloat16), ref, bound)  # the rounded reference alone
+        sref, sbound = P.row_stats_bound(x, P.LN_EPS)
+        ws = P.assert_elementwise(emulate_ln(x, gamma, beta, None, P.LN_EPS, order, stats_only=True), sref, sbound)
+        P.assert_elementwise(sref.float(), sref, sbound)
+    print(f"layernorm emulation C {C} mean {mean_sigmas} {order}: err/bound {worst:.3f}, stats {ws:.3f}")
+
+
+def test_layernorm_neighbour_statistics_rejected():
+    rows, C = 257, 320
+    _, gamma, beta, _ = P.ln_case(rows, C, 0)
+    x = P.bf16_round(rnd(rows, C, seed=3))  # rows of one distribution: the neighbour's statistics are close
+    ref, bound = P.ln_bound(x, gamma, beta, None, P.LN_EPS, torch.bfloat16)
+    got = emulate_ln(x, gamma, beta, None, P.LN_EPS)
+    st = emulate_ln(x, gamma, beta, None, P.LN_EPS, stats_only=True)
+    r = 130
+    got[r] = ((x[r] - st[r + 1, 0]) * st[r + 1, 1] * gamma + beta).to(torch.bfloat16).float()
+    with pytest.raises(AssertionError, match=rf"row {r},"):
+        P.assert_elementwise(got, ref, bound)
+    assert rel_err(got, ref) < 1e-2
+    sref, sbound = P.row_stats_bound(x, P.LN_EPS)
+    st[r] = st[r + 1]
+    with pytest.raises(AssertionError, match=rf"row {r},"):
+        P.assert_elementwise(st, sref, sbound)
+
+
+def test_layernorm_wrong_frame_pe_rejected():
+    """The first row after a frame boundary still gets the previous frame's pe row."""
+    rows, C = 6000, 136
+    x, gamma, beta, pe = P.ln_case(rows, C, 0)
+    pe_row = P.ln_pe_rows(pe, rows)
+    ref, bound = P.ln_bound(x, gamma, beta, pe_row, P.LN_EPS, torch.bfloat16)
+    bad = pe_row.clone()
+    r = 5 * P.LN_PE_RPF
+    bad[r] = pe_row[r - 1]
+    got = emulate_ln(x, gamma, beta, bad, P.LN_EPS)
+    with pytest.raises(AssertionError, match=rf"row {r},"):
+        P.assert_elementwise(got, ref, bound)
+    assert rel_err(got, ref) < 1e-2
+
+
+@pytest.mark.parametrize("C", [136, 320])
+def test_layernorm_truncation_rejected(C):
+    x, gamma, beta, _ = P.ln_case(33, C, 0)
+    ref, bound = P.ln_bound(x, gamma, beta, None, P.LN_EPS, torch.bfloat16)
+    got = emulate_ln(x, gamma, beta, None, P.LN_EPS, truncate=True)
+    with pytest.raises(AssertionError, match="err/bound"):
+        P.assert_elementwise(got, ref, bound)
+    assert rel_err(got, ref) < 1e-2
+
+
+def test_ln_propagate_covers_a_perturbed_input():
+    """|d a| of a = (x - mu) r under |dx| <= b, for the worst-sign and for random perturbations."""
+    x, _, _, _ = P.ln_case(33, 320, 3)
+    x = P.f64(x)
+    b = 2.0 ** -8 * x.abs()
+
+    def norm(v):
+        d = v - v.mean(-1, keepdim=True)
+        r = 1.0 / torch.sqrt((d * d).mean(-1, keepdim=True) + P.LN_EPS)
+        return d * r, r
+
+    a, r = norm(x)
+    bound = P.ln_propagate(a, r, b) * P.SLACK
+    worst = 0.0
+    for seed, sign in enumerate([torch.sign(a), -torch.sign(a), None, None, None]):
+        s = sign if sign is not None else torch.sign(rnd(*x.shape, seed=seed).double())
+        worst = max(worst, P.assert_elementwise(norm(x + s * b)[0], a, bound))
+    print(f"ln_propagate: err/bound {worst:.3f}")
+    assert worst > 0.2
+
+
+# ---------------------------------------------------------------- GroupNorm statistics
+def emulate_gn_stats(x, groups, eps, gamma, beta, nsplit, R, order="forward", naive_group=None):
+    """gn_stats_kernel: per (split, thread row r, channel) an fp32 chain over every R-th row of
+    the split of d = x - k_g and d * d ("fma": the square added unrounded), fp64 from there on.
+    naive_group: that group's variance as fp32 E[x^2] - E[x]^2 of unshifted fp32 sums."""
+    S, pps, C = x.shape
+    cpg = C // groups
+    k = x[:, :1, ::cpg].repeat_interleave(cpg, 2)
+    d = x - k
+    S1 = torch.zeros(S, C, dtype=torch.float64)
+    S2 = torch.zeros(S, C, dtype=torch.float64)
+    for split in range(nsplit):
+        p0, p1 = pps * split // nsplit, pps * (split + 1) // nsplit
+        seg = d[:, p0:p1]
+        n_t = -(-(p1 - p0) // R)
+        seg = torch.cat([seg, torch.zeros(S, n_t * R - (p1 - p0), C)], 1).reshape(S, n_t, R, C)
+        a1, a2 = torch.zeros(S, R, C), torch.zeros(S, R, C)
+        ts = range(n_t) if order != "backward" else range(n_t - 1, -1, -1)
+        for t in ts:
+            a1 = a1 + seg[:, t]
+            a2 = (a2.double() + seg[:, t].double() ** 2).float() if order == "fma" else a2 + seg[:, t] * seg[:, t]
+        S1 += a1.double().sum(1)
+        S2 += a2.double().sum(1)
+    n = float(pps * cpg)
+    m1 = S1.reshape(S, groups, cpg).sum(-1) / n
+    var = (S2.reshape(S, groups, cpg).sum(-1) / n - m1 * m1).clamp_min(0.0)
+    mean = (x[:, 0, ::cpg].double() + m1).float()
+    rstd = (1.0 / torch.sqrt(var + eps)).float()
+    if naive_group is not None:
+        xg = x.reshape(S, pps, groups, cpg)[:, :, naive_group]
+        m = xg.sum((1, 2)) / n
+        v = (xg * xg).sum((1, 2)) / n - m * m
+        rstd[:, naive_group] = torch.rsqrt(v.clamp_min(0.0) + eps)
+    sc = gamma * rstd.repeat_interleave(cpg, 1)
+    return sc, beta - mean.repeat_interleave(cpg, 1) * sc
+
+
+def gn_check(got, ref, bound, name):
+    ws = P.assert_elementwise(got[0], ref[0], bound[0], name=f"{name} scale")
+    return max(ws, P.assert_elementwise(got[1], ref[1], bound[1], name=f"{name} shift"))
+
+
+@pytest.mark.parametrize("name,C1,C2,groups,n_samples,pps", P.GN_CASES, ids=[c[0] for c in P.GN_CASES])
+@pytest.mark.parametrize("mean_sigmas", P.GN_MEANS)
+def test_groupnorm_stats_emulation_passes(name, C1, C2, groups, n_samples, pps, mean_sigmas):
+    C = C1 + C2
+    x, gamma, beta = P.gn_case(C1, C2, n_samples, pps, mean_sigmas)
+    R = P.gn_R(C)
+    ns = P.gn_nsplit(n_samples, pps, C)
+    worst = 0.0
+    # the launcher's split with three summation orders, and the extreme splits (one block per
+    # sample: the longest per-thread chains; one block per 8 R rows, at most 4096: the shortest)
+    runs = [(ns, o) for o in ("forward", "backward", "fma")]
+    runs += [(e, "forward") for e in {1, max(1, min(pps // (8 * R), 4096))} - {ns} if C * pps <= 4096 * 320]
+    for nsplit, order in runs:
+        ref, bound = P.gn_stats_bound(x, groups, P.GN_EPS, gamma, beta, nsplit, R)
+        got = emulate_gn_stats(x, groups, P.GN_EPS, gamma, beta, nsplit, R, order)
+        worst = max(worst, gn_check(got, ref, bound, f"{name} nsplit {nsplit} {order}"))
+    gn_check((ref[0].float(), ref[1].float()), ref, bound, f"{name} rounded reference")
+    print(f"groupnorm stats emulation {name} mean {mean_sigmas}: err/bound {worst:.3f}")
+
+
+def test_groupnorm_unshifted_variance_rejected():
+    """One group's variance as E[x^2] - E[x]^2 in fp32 at mean / std = 30: 900 parts of cancellation."""
+    C, groups, S, pps = 320, 32, 3, 4096
+    x, gamma, beta = P.gn_case(C, 0, S, pps, 30)
+    R, ns = P.gn_R(C), P.gn_nsplit(S, pps, C)
+    ref, bound = P.gn_stats_bound(x, groups, P.GN_EPS, gamma, beta, ns, R)
+    got = emulate_gn_stats(x, groups, P.GN_EPS, gamma, beta, ns, R, naive_group=17)
+    with pytest.raises(AssertionError, match="err/bound"):
+        P.assert_elementwise(got[0], ref[0], bound[0])
+    ratio = (P.f64(got[0]) - ref[0]).abs() / bound[0]
+    cols = sorted(set(torch.nonzero(ratio > 1.0)[:, 1].tolist()))
+    assert cols and all(c // 10 == 17 for c in cols), cols
+    print(f"unshifted variance: err/bound {float(ratio.max()):.1f}, Frobenius {rel_err(got[0], ref[0]):.2e}")
+    assert rel_err(got[0], ref[0]) < 1e-2 and rel_err(got[1], ref[1]) < 1e-2
+
+
+@pytest.mark.parametrize("cpg,slots,C1,C2", P.GN_COLSUM_CASES)
+def test_groupnorm_colsum_emulation_passes(cpg, slots, C1, C2):
+    cs1, cs2, gamma, beta = P.gn_colsum_case(cpg, slots, C1, C2)
+    cs = cs1 if cs2 is None else torch.cat([cs1, cs2], 2)
+    ref, bound = P.gn_colsum_bound(cs, slots, 32, P.GN_EPS, gamma, beta)
+    n = float(slots * 128 * cpg)
+    t = cs.double().reshape(3, slots, 2, 32, cpg)
+    worst = 0.0
+    for flip in (False, True):  # two fp64 summation orders
+        tt = t.flip(1, 4) if flip else t
+        s1, s2 = tt[:, :, 0].sum((1, 3)), tt[:, :, 1].sum(3).sum(1)
+        mean = s1 / n
+        rstd = (1.0 / torch.sqrt((s2 / n - mean * mean).clamp_min(0.0) + P.GN_EPS)).float()
+        sc = gamma * rstd.repeat_interleave(cpg, 1)
+        sh = beta - mean.float().repeat_interleave(cpg, 1) * sc
+        worst = max(worst, gn_check((sc, sh), ref, bound, "colsum finalize"))
+    # the bound is not vacuous: a variance off by 1e-5 of itself is outside it
+    bad = gamma * (1.0 / torch.sqrt(((s2 / n - mean * mean) * (1 + 1e-5)) + P.GN_EPS)).float().repeat_interleave(cpg, 1)
+    with pytest.raises(AssertionError):
+        P.assert_elementwise(bad, ref[0], bound[0])
+    print(f"groupnorm colsum emulation cpg {cpg} slots {slots} C1 {C1}: err/bound {worst:.3f}")
+
+
+@pytest.mark.parametrize("M", [128, 384])
+@pytest.mark.parametrize("N", [8, 40, 320])
+def test_colsum_emulation_passes(M, N):
+    y = P.bf16_round(rnd(M, N, seed=M + N) + 2.0)
+    ref, bound = P.colsum_bound(y)
+    t = y.reshape(M // 128, 128, N)
+    for order in ("kernel", "pairwise"):
+        if order == "kernel":  # 8 row lanes of 16 rows each, then merged in turn
+            s1, s2 = torch.zeros(M // 128, 8, N), torch.zeros(M // 128, 8, N)
+            for r in range(16):
+                s1, s2 = s1 + t[:, 8 * r:8 * r + 8], (s2.double() + t[:, 8 * r:8 * r + 8].double() ** 2).float()
+            a1, a2 = s1[:, 0], s2[:, 0]
+            for k in range(1, 8):
+                a1, a2 = a1 + s1[:, k], a2 + s2[:, k]
+        else:
+            a1, a2 = t.sum(1), (t * t).sum(1)
+        worst = P.assert_elementwise(torch.stack([a1, a2], 1), ref, bound)
+    P.assert_elementwise(ref.float(), ref, bound)
+    got = torch.stack([a1, a2], 1)
+    got[0, 0, N - 1] -= t[0, 127, N - 1]  # one row left out of one column
+    with pytest.raises(AssertionError, match="err/bound"):
+        P.assert_elementwise(got, ref, bound)
+    print(f"colsum emulation {M}x{N}: err/bound {worst:.3f}")
+
+
+@pytest.mark.parametrize("name,C1,C2,S,pps", P.GN_APPLY_CASES, ids=[c[0] for c in P.GN_APPLY_CASES])
+@pytest.mark.parametrize("silu", [False, True])
+def test_groupnorm_apply_emulation_passes(name, C1, C2, S, pps, silu):
+    x, scale, shift = apply_case(C1, C2, S, pps)
+    ref, bound = P.gn_apply_bound(x, scale, shift, silu)
+    pre = x * scale[:, None] + shift[:, None]
+    got = (F.silu(pre) if silu else pre).to(torch.bfloat16).float()
+    worst = P.assert_elementwise(got, ref, bound)
+    P.assert_elementwise(ref.to(torch.bfloat16), ref, bound)
+    print(f"groupnorm apply emulation {name} silu {silu}: err/bound {worst:.3f}")
+
+
+def apply_case(C1, C2, S, pps, seed=0, mean_sigmas=2):
+    """x and the fp32 (scale, shift) of its own 32-group GroupNorm (so neighbouring samples have
+    nearly equal affines, as in the model)."""
+    x, gamma, beta = P.gn_case(C1, C2, S, pps, mean_sigmas, seed=seed)
+    (sc, sh), _ = P.gn_stats_bound(x, 32, P.GN_EPS, gamma, beta, 1, 1)
+    return x, sc.float(), sh.float()
+
+
+def test_groupnorm_apply_previous_sample_affine_rejected():
+    """The first block pass (ppb = 16 pixels at C = 128) of sample 1 with sample 0's (scale, shift)."""
+    C, S, pps = 128, 3, 1024
+    x, scale, shift = apply_case(C, 0, S, pps, mean_sigmas=0)  # samples of one distribution: nearly equal affines
+    ref, bound = P.gn_apply_bound(x, scale, shift, True)
+    pre = x * scale[:, None] + shift[:, None]
+    pre[1, :16] = x[1, :16] * scale[0] + shift[0]
+    got = F.silu(pre).to(torch.bfloat16).float()
+    with pytest.raises(AssertionError, match="err/bound"):
+        P.assert_elementwise(got.reshape(S * pps, C), ref.reshape(S * pps, C), bound.reshape(S * pps, C))
+    ratio = ((P.f64(got) - ref).abs() / bound).reshape(S * pps, C).amax(1)
+    bad = torch.nonzero(ratio > 1.0).reshape(-1)
+    assert int(bad.min()) >= pps and int(bad.max()) < pps + 16
+    print(f"previous sample's affine: err/bound {float(ratio.max()):.1f}, Frobenius {rel_err(got, ref):.2e}")
+    assert rel_err(got, ref) < 1e-2
+
+
+# ---------------------------------------------------------------- fused FeedForward kernels
+def bfr(t):
+    return t.to(torch.bfloat16).float()
+
+
+def mm(a, w, order):
+    """a w^T in fp32: torch's own order, or 32-wide k-steps accumulated in turn (the MFMA loop)."""
+    if order == "torch":
+        return a @ w.T
+    acc = torch.zeros(a.shape[0], w.shape[0])
+    for k in range(0, a.shape[1], 32):
+        acc = acc + a[:, k:k + 32] @ w[:, k:k + 32].T
+    return acc
+
+
+def ff_body(a, c, order, swap=None, drop=None):
+    """GEGLU(W1 a + b1) W2^T in fp32 with G rounded to bf16; swap = two inner columns of W2
+    exchanged (a packing permutation off by one slot); drop = (rows, chunk): that 32-column
+    inner chunk never accumulated for those rows."""
+    pre = mm(a, c["w1g"], order) + c["b1f"].float()
+    G = bfr(pre[:, :P.FF_INNER] * F.gelu(pre[:, P.FF_INNER:]))
+    w2 = c["w2r"]
+    if swap is not None:
+        w2 = w2.clone()
+        w2[:, list(swap)] = w2[:, list(reversed(swap))]
+    if drop is not None:
+        G = G.clone()
+        G[drop[0], 32 * drop[1]:32 * drop[1] + 32] = 0.0
+    return mm(G, w2, order)
+
+
+def emulate_ff(c, order="torch", **defect):
+    x, st = c["x"], c["stats"]
+    a = bfr(torch.addcmul(-(st[:, :1] * st[:, 1:]), x, st[:, 1:]))
+    return bfr(ff_body(a, c, order, **defect) + c["b2"] + x)
+
+
+def ff_ref(c):
+    return P.ff_bound(c["x"], c["stats"], c["w1g"], c["b1f"], c["b1_mag"], c["w2r"], c["b2"])
+
+
+@pytest.mark.parametrize("M", P.FF_M)
+def test_feedforward_emulation_passes(M):
+    c = P.ff_case(M)
+    ref, bound = ff_ref(c)
+    for order in ("torch", "ksteps"):
+        worst = P.assert_elementwise(emulate_ff(c, order), ref, bound)
+    P.assert_elementwise(ref.to(torch.bfloat16), ref, bound)
+    print(f"feedforward emulation M {M}: err/bound {worst:.3f}")
+
+
+def _rejected(got, ref, bound, what):
+    with pytest.raises(AssertionError, match="err/bound"):
+        P.assert_elementwise(got, ref, bound)
+    worst = float(((P.f64(got) - ref).abs() / bound).max())
+    fro = rel_err(got, ref)
+    print(f"{what}: err/bound {worst:.1f}, Frobenius {fro:.2e}")
+    assert fro < 1e-2  # on record: the Frobenius ratio passes it
+    return worst
+
+
+@pytest.mark.parametrize("swap", [(1, 2), (33, 34), (29, 30), (1277, 1278)])
+def test_feedforward_swapped_w2_columns_rejected(swap):
+    c = P.ff_case(300)
+    ref, bound = ff_ref(c)
+    _rejected(emulate_ff(c, swap=swap), ref, bound, f"W2 inner columns {swap} swapped")
+
+
+@pytest.mark.parametrize("swap", [(3, 4), (15, 16), (31, 32), (1278, 1279)])
+def test_feedforward_swapped_needle_columns_far_outside(swap):
+    """A swap that involves a needle column (8 times the weight) is two orders outside."""
+    c = P.ff_case(129)
+    ref, bound = ff_ref(c)
+    worst = float(((P.f64(emulate_ff(c, swap=swap)) - ref).abs() / bound).max())
+    print(f"W2 needle columns {swap} swapped: err/bound {worst:.1f}")
+    assert worst > 50
+
+
+@pytest.mark.parametrize("chunk", [5, 17, 38])
+def test_feedforward_dropped_chunk_rejected(chunk):
+    """One wave (16 rows of 1200) skips one 32-column inner chunk."""
+    c = P.ff_case(1200)
+    ref, bound = ff_ref(c)
+    _rejected(emulate_ff(c, drop=(slice(640, 656), chunk)), ref, bound, f"inner chunk {chunk} dropped for 16 rows")
+
+
+@pytest.mark.parametrize("k", P.FF_W1_NEEDLES)
+def test_feedforward_dropped_w1_k_column_rejected(k):
+    c = P.ff_case(300)
+    ref, bound = ff_ref(c)
+    c2 = dict(c, w1g=c["w1g"].clone())
+    c2["w1g"][:, k] = 0.0
+    with pytest.raises(AssertionError, match="err/bound"):
+        P.assert_elementwise(emulate_ff(c2), ref, bound)
+
+
+def emulate_ff_chain(c, order="torch"):
+    C = P.FF_C
+    h2 = bfr(mm(c["o"], c["wor"], order) + c["bo"] + c["h1"])
+    mean = h2.sum(1, keepdim=True) * (1.0 / C)
+    d = h2 - mean
+    rstd = torch.rsqrt((d * d).sum(1, keepdim=True) * (1.0 / C) + 1e-5)
+    a = bfr(d * rstd)
+    y = bfr(ff_body(a, c, order) + (h2 + c["b2"]))
+    z = bfr(mm(y, c["wpr"], order) + c["bp"] + c["xb"])
+    t = z.reshape(-1, 128, C)
+    return z, torch.stack([t.sum(1), (t * t).sum(1)], 1)
+
+
+def ff_chain_ref(c):
+    return P.ff_chain_bound(c["o"], c["h1"], c["xb"], c["wor"], c["bo"], c["w1g"], c["b1f"], c["b1_mag"], c["w2r"],
+                            c["b2"], c["wpr"], c["bp"], 1e-5)
+
+
+@pytest.mark.parametrize("M", P.FF_CHAIN_M)
+def test_ff_chain_emulation_passes(M):
+    c = P.ff_chain_case(M)
+    ref, bound = ff_chain_ref(c)
+    for order in ("torch", "ksteps"):
+        z, cs = emulate_ff_chain(c, order)
+        worst = P.assert_elementwise(z, ref, bound)
+        wc = P.assert_elementwise(cs, *P.colsum_bound(z))
+    P.assert_elementwise(ref.to(torch.bfloat16), ref, bound)
+    print(f"ff_chain emulation M {M}: err/bound {worst:.3f}, column sums {wc:.3f}")
+    # a proj_out that forgets the block input on one row is outside the bound
+    z[77] = z[77] - c["xb"][77]
+    with pytest.raises(AssertionError, match="row 77,"):
+        P.assert_elementwise(z, ref, bound)
+
+
+# ---------------------------------------------------------------- fused attention kernels
+def emulate_xattn(c, L, order="torch", leak_rows=None, drop_tail=None):
+    """xattn_fused_kernel in fp32 / bf16.  leak_rows: for those query rows one zero key >= L stays
+    unmasked (score 0, value 0: only the row sum grows); drop_tail = (rows, head): dims 32 .. 39
+    of that head never reach the out-projection for those rows."""
+    C, H, D, hw = 320, 8, 40, P.XA_HW
+    x, st = c["x"], c["stats"]
+    M = x.shape[0]
+    n = M // hw
+    a = bfr(torch.addcmul(-(st[:, :1] * st[:, 1:]), x, st[:, 1:]))
+    q = bfr(mm(a, c["wqr"], order) + c["bqf"].float())
+    q4 = q.reshape(n, hw, H, D).permute(0, 2, 1, 3)
+    k = c["kv"][:, :C].reshape(n, L, H, D).permute(0, 2, 1, 3)
+    v = c["kv"][:, C:].reshape(n, L, H, D).permute(0, 2, 1, 3)
+    s = q4 @ k.transpose(-1, -2)
+    mx = s.amax(-1, keepdim=True)
+    leak = torch.zeros(M, dtype=torch.bool)
+    if leak_rows is not None:
+        leak[leak_rows] = True
+        mx = torch.where(leak.reshape(n, 1, hw, 1), mx.clamp_min(0.0), mx)
+    p = bfr(torch.exp2(s - mx))
+    l = p.sum(-1, keepdim=True) + torch.where(leak.reshape(n, 1, hw, 1), bfr(torch.exp2(-mx)), torch.zeros(()))
+    o = bfr((p @ v) * (1.0 / l)).permute(0, 2, 1, 3).reshape(M, C)
+    if drop_tail is not None:
+        o = o.clone()
+        o[drop_tail[0], 40 * drop_tail[1] + 32:40 * drop_tail[1] + 40] = 0.0
+    y = bfr(mm(o, c["wor"], order) + c["bo"] + x)
+    t = y.reshape(M, 10, 32)  # statistics of the stored rows: fp32 per 32-column chunk, then fp64
+    s1, s2 = t.sum(-1).double().sum(-1) / C, (t * t).sum(-1).double().sum(-1) / C
+    stats = torch.stack([s1, 1.0 / torch.sqrt((s2 - s1 * s1).clamp_min(0.0) + 1e-5)], 1).float()
+    return y, stats
+
+
+def xattn_ref(c, L):
+    return P.xattn_bound(c["x"], c["stats"], c["wqr"], c["bqf"], c["bq_mag"], c["kv"], L, P.XA_HW, c["wor"], c["bo"])
+
+
+@pytest.mark.parametrize("L", P.XA_L)
+def test_xattn_emulation_passes(L):
+    c = P.xattn_case(L)
+    ref, bound = xattn_ref(c, L)
+    for order in ("torch", "ksteps"):
+        y, st = emulate_xattn(c, L, order)
+        worst = P.assert_elementwise(y, ref, bound)
+        ws = P.assert_elementwise(st, *P.stored_row_stats_bound(y, 1e-5))
+    P.assert_elementwise(ref.to(torch.bfloat16), ref, bound)
+    print(f"xattn emulation L {L}: err/bound {worst:.3f}, statistics {ws:.3f}")
+
+
+@pytest.mark.parametrize("L", [5, 7])
+def test_xattn_unmasked_key_rejected(L):
+    """One query row keeps key slot L (zeros in LDS) in the softmax."""
+    c = P.xattn_case(L)
+    ref, bound = xattn_ref(c, L)
+    y, _ = emulate_xattn(c, L, leak_rows=slice(150, 151))
+    _rejected(y, ref, bound, f"key {L} of {L} left unmasked for one row")
+
+
+@pytest.mark.parametrize("L,head", [(50, 0), (50, 7), (64, 3)])
+def test_xattn_dropped_head_tail_rejected(L, head):
+    """Eight rows lose dims 32 .. 39 of one head (the third k-step of its head pair)."""
+    c = P.xattn_case(L)
+    ref, bound = xattn_ref(c, L)
+    y, _ = emulate_xattn(c, L, drop_tail=(slice(272, 280), head))
+    _rejected(y, ref, bound, f"head {head} dims 32..39 dropped in the out-projection")
+
+
+def emulate_tattn(c, C, S, Fr, order="torch", leak=None):
+    """tattn_fused_kernel in fp32 / bf16; leak = (sample, pixel, head): frame Fr (a zero row,
+    whose LayerNorm is beta + pe[Fr]) stays in that pixel's softmax for that head."""
+    H, B = 8, P.TA_SAMPLES
+    D = C // H
+    x = c["x"]
+    frame = (torch.arange(x.shape[0]) // S) % Fr
+    mean = x.sum(1, keepdim=True) * (1.0 / C)
+    d = x - mean
+    rstd = torch.rsqrt((d * d).sum(1, keepdim=True) * (1.0 / C) + 1e-5)
+    ln = bfr(torch.addcmul(c["bpe"][frame], d * rstd, c["gamma"]))
+    if leak is not None:  # one more row per (sample, pixel): frame Fr of every pixel, used for one only
+        Fe = Fr + 1
+        lne = torch.zeros(B, Fe, S, C)
+        lne[:, :Fr] = ln.reshape(B, Fr, S, C)
+        lne[:, Fr] = bfr(c["bpe"][Fr])
+        ln, Fk = lne.reshape(B * Fe * S, C), Fe
+    else:
+        Fk = Fr
+    q, k, v = (bfr(mm(ln, w, order)).reshape(B, Fk, S, H, D).permute(0, 2, 3, 1, 4) for w in (c["wqp"], c["wkr"], c["wvr"]))
+    s = q @ k.transpose(-1, -2)  # (B, S, H, Fk, Fk), log2 units
+    if leak is not None:
+        mask = torch.ones(B, S, H, dtype=torch.bool)
+        mask[leak] = False
+        s[..., Fr] = torch.where(mask[..., None], torch.full_like(s[..., Fr], -float("inf")), s[..., Fr])
+    p = bfr(torch.exp2(s - s.amax(-1, keepdim=True)))
+    o = bfr((p @ v) * (1.0 / p.sum(-1, keepdim=True)))[:, :, :, :Fr]
+    return o.permute(0, 3, 1, 2, 4).reshape(B * Fr * S, C)
+
+
+def tattn_ref(c, S, Fr):
+    return P.tattn_bound(c["x"], c["gamma"], c["bpe"], c["wqp"], c["wkr"], c["wvr"], P.TA_SAMPLES, Fr, S, 8, 1e-5)
+
+
+@pytest.mark.parametrize("C,S", P.TA_CASES)
+@pytest.mark.parametrize("Fr", P.TA_F)
+def test_tattn_emulation_passes(C, S, Fr):
+    c = P.tattn_case(C, S, Fr)
+    ref, bound = tattn_ref(c, S, Fr)
+    for order in ("torch", "ksteps"):
+        worst = P.assert_elementwise(emulate_tattn(c, C, S, Fr, order), ref, bound)
+    P.assert_elementwise(ref.to(torch.bfloat16), ref, bound)
+    print(f"temporal attention emulation C {C} F {Fr}: err/bound {worst:.3f}")
+
+
+@pytest.mark.parametrize("C,S,Fr", [(320, 64, 5), (640, 64, 7), (640, 64, 5)])
+def test_tattn_unmasked_frame_rejected(C, S, Fr):
+    c = P.tattn_case(C, S, Fr)
+    ref, bound = tattn_ref(c, S, Fr)
+    got = emulate_tattn(c, C, S, Fr, leak=(1, 37, 4))
+    P.assert_elementwise(emulate_tattn(c, C, S, Fr), ref, bound)
+    _rejected(got, ref, bound, f"frame {Fr} of {Fr} left unmasked for one pixel and head")
+
+
+# ---------------------------------------------------------------- attn_bound's input-error terms
+def test_attn_bound_input_errors_cover_a_perturbation():
+    q, k, v = (P.bf16_round(rnd(2, 2, n, 40, seed=s)) for n, s in ((33, 1), (20, 2), (20, 3)))
+    scale = 1 / math.sqrt(40)
+    ref0, b0 = P.attn_bound(q, k, v, scale)
+    bq, bk, bv = (2.0 ** -8 * t.abs() for t in (q, k, v))
+    ref, b = P.attn_bound(q, k, v, scale, q_err=bq, k_err=bk, v_err=bv)
+    assert torch.equal(ref, ref0) and bool((b > b0).all())
+    assert torch.equal(P.attn_bound(q, k, v, scale, q_err=0 * bq, k_err=0 * bk, v_err=0 * bv)[1], b0)
+    worst = 0.0
+    for seed in range(4):
+        sg = [torch.sign(rnd(*t.shape, seed=10 * seed + i)) for i, t in enumerate((q, k, v))]
+        got = P.attn_bound(q + sg[0] * bq, k + sg[1] * bk, v + sg[2] * bv, scale)[0]
+        worst = max(worst, P.assert_elementwise(got, ref, b - b0 * (1 - 2.0 ** -6)))  # the input terms alone
+    print(f"attn_bound input errors: err/bound {worst:.3f}")
+    assert worst > 0.05
