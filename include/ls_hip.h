@@ -456,25 +456,24 @@ int ls_paste_back(const uint16_t* dec, int32_t ld_dec, const uint16_t* pix, int3
 int ls_add_rows(const uint16_t* x, int64_t rows, int32_t C, int32_t ldx, const float* table, int32_t table_rows,
                 uint16_t* y, int32_t ldy, void* stream);
 
-/* Tuning / A-B switches for ls_conv2d (process-wide, host side only):
+/* Tuning / A-B switches for ls_conv2d (process-wide, host side only); any other key, or a value
+ * a key does not take, is LS_ERR_INVALID:
  * key 1 = force the register-staged kernel (1) instead of the LDS-DMA one;
- * key 2 = force tile 0 auto, 1 128x128, 2 128x64, 3 64x64, 4 128x32; key 3 = split-K with key 2;
+ * key 2 = force tile 0 auto, 1 128x128, 2 128x64, 3 64x64, 4 128x32, 5 256x256, 6 256x128,
+ * 9 128x160; key 3 = split-K with key 2;
  * key 4 = ablation (1 skip MFMA, 2 skip operand DMA, 4 skip the output store, 8 the general epilogue
- * arithmetic; timing only); key 5 = DMA K-tile depth 32 or 64;
+ * arithmetic; timing only);
  * key 6 = row-block GEMM on / off; key 7 = its K = 640 instances on / off; key 8 = halo-tile 3x3
- * conv on / off (ABI 12); key 9 = d = 40 self attention on the 32x32x16 kernel (ABI 12);
- * key 10 = 256x128 3-stage tile for the short-K linears; key 11 = register-staged operand loads in
- * the tiled GEMM; key 12 = halo pieces over the read pixels only (default on); key 13 = 128-channel
- * halo tiles where 160 also divides N; key 14 = 1x1 GEMM with A straight into registers.  Keys 10, 11,
- * 13, 14 are measured-slower A/B options; key 15 = K = 640 row-block GEMM with two
- * 16-row fragments per wave (256-row blocks; default on); key 16 = 128-column halo tiles on 16 x 8
- * patches, two blocks per CU, for Cin <= 256 (default on; off: 16 x 16, one block per CU);
- * key 17 = ls_ff_chain rows per wave: 1 = 16 rows (default), 2 = 32 rows, one wave per SIMD
- * (measured slower; diagnostics build only); key 18 = nearest-x2 upsample convs on the halo-tile
- * kernel (default on; off: the tiled gather); key 19 = the narrow 16-column halo tile for 3x3 convs
- * with N = 8 / 16 (the VAE's conv_out with conv_norm_out + SiLU fused; default on; off: the tiled
- * 128 x 32 GEMM); key 20 = the K = 640 residual linears on the row-block GEMM (default off: the
- * tiled 128 x 160 kernel). */
+ * conv on / off (ABI 12); key 9 = attention kernel variant: 0 only (the one there is);
+ * key 12 = halo pieces over the read pixels only: 1 only; key 13 = 128-channel halo tiles where
+ * 160 also divides N (measured slower; default off);
+ * key 15 = K = 640 row-block GEMM with two 16-row fragments per wave (256-row blocks; default on);
+ * key 16 = 128-column halo tiles on 16 x 8 patches, two blocks per CU, for Cin <= 256 (default on;
+ * off: 16 x 16, one block per CU); key 17 = ls_ff_chain rows per wave: 1 (16 rows) only;
+ * key 18 = nearest-x2 upsample convs on the halo-tile kernel (default on; off: the tiled gather);
+ * key 19 = the narrow 16-column halo tile for 3x3 convs with N = 8 / 16 (the VAE's conv_out with
+ * conv_norm_out + SiLU fused; default on; off: the tiled 128 x 32 GEMM); key 20 = the K = 640
+ * residual linears on the row-block GEMM (default off: the tiled 128 x 160 kernel). */
 int ls_set_tuning(int32_t key, int32_t value);
 
 /* Diagnostics: workgroups per CU the runtime can co-schedule for a GEMM kernel

@@ -12,17 +12,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LS_HIP_LIB", os.path.join(HERE, "libls_hip.so"))
 ABI_VERSION = 14
 
-
-
-def ab_switch(name: str, default: str) -> str:
-    """An A/B switch of the host dispatch, read from the environment ONLY in diagnostics
-    mode (LS_DIAG_BUILD=1, the same flag that builds the library's A/B kernels): the
-    default product path does not depend on the environment."""
-    if os.environ.get("LS_DIAG_BUILD", "") in ("", "0"):
-        return default
-    return os.environ.get(name, default)
-
-
 c_u16p = C.c_void_p
 c_vp = C.c_void_p
 
@@ -181,11 +170,6 @@ def load(path: str = None):
         fn.argtypes = args
     if lib.ls_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libls_hip.so ABI {lib.ls_abi_version()} != {ABI_VERSION}; rebuild it")
-    # diagnostics A/B runs: LS_TUNE="key=value,..." applied through ls_set_tuning
-    for kv in filter(None, ab_switch("LS_TUNE", "").split(",")):
-        k, v = (int(t) for t in kv.split("="))
-        if lib.ls_set_tuning(k, v) != 0:
-            raise RuntimeError(f"LS_TUNE {kv}: {lib.ls_last_error().decode()}")
     _lib = lib
     return lib
 

@@ -1,13 +1,12 @@
 """Builds libls_hip.so (all HIP kernels + the C-ABI) in-tree for gfx950.
 
     python -m latentsync_amd.build        # incremental
-    LS_DIAG_BUILD=1 python -m latentsync_amd.build   # + the measured-and-rejected kernels
 Compiles each csrc/*.hip with hipcc --offload-arch=gfx950 -O3 -fPIC into
-build/ objects and links latentsync_amd/libls_hip.so.  No CUDA, no dual path.
-The default build compiles only the kernels the dispatch uses; the diagnostics build
-(-DLS_DIAG_KERNELS, objects in build/obj_diag) adds the A/B variants DESIGN.md section 3
-records as measured and rejected (register-staged / A-in-register / phased / 4-stage GEMMs,
-the 256x128 3-stage tile, BK 32, attn6) for re-measurement.
+build/obj and links latentsync_amd/libls_hip.so.  No CUDA, no dual path, one build.
+The variants DESIGN.md section 3 records as measured and rejected (register-staged /
+A-in-register / phased / 4-stage GEMMs, the 256x128 3-stage tile, BK 32, attn6, the pair
+FeedForward, ff_chain at 32 rows per wave) are not in the tree; commit f51e7ce is the last
+one that holds their code.
 """
 import concurrent.futures as cf
 import os
@@ -21,9 +20,7 @@ import warnings
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-DIAG = os.environ.get("LS_DIAG_BUILD", "") not in ("", "0")
-OBJ = os.path.join(REPO, "build", "obj_diag" if DIAG else "obj")
-MODE_STAMP = os.path.join(REPO, "build", "lib_mode")
+OBJ = os.path.join(REPO, "build", "obj")
 LIB = os.path.join(HERE, "libls_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize: no v_pk_*_f32 packed fp32 math.  (1) Beside MFMAs it costs
@@ -33,7 +30,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # produced intermittently wrong values on gfx950 -- second wave of a SIMD, run to
 # run different -- and bit-exact results without packing (scripts/debug_rb3.py).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result", "-munsafe-fp-atomics",
-         "-fno-slp-vectorize"] + (["-DLS_DIAG_KERNELS"] if DIAG else [])
+         "-fno-slp-vectorize"]
 
 
 def _deps():
@@ -47,8 +44,7 @@ def _deps():
 # so the build refuses any spill in them (hipcc resource-usage remarks).
 # tests/test_build_guards.py checks that every kernel with a non-zero counted wait in csrc/ is listed.
 COUNTED_VMCNT = ("gemm_rowblock_kernel", "conv_gemm_dma_kernel", "attn5_kernel", "attn8_kernel", "tattn_fused_kernel",
-                 "attnw_kernel", "conv3x3_halo_kernel", "attn6_kernel", "conv_gemm_p8_kernel", "conv_gemm_big4_kernel",
-                 "conv_gemm_areg_kernel", "ff_pair_kernel", "ff_chain_kernel")
+                 "attnw_kernel", "conv3x3_halo_kernel", "ff_chain_kernel")
 
 
 def _spills(stderr):
@@ -130,17 +126,13 @@ def build(verbose=True):
             if err:
                 raise RuntimeError(f"hipcc failed for {obj}:\n{err}")
             objs.append(obj)
-    mode = "diag" if DIAG else "default"
-    old_mode = open(MODE_STAMP).read().strip() if os.path.exists(MODE_STAMP) else "default"
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(o) for o in objs) or old_mode != mode:
+    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(o) for o in objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed:\n" + r.stderr)
-        with open(MODE_STAMP, "w") as f:
-            f.write(mode + "\n")
         if verbose:
-            print("built", LIB, f"({mode})")
+            print("built", LIB)
     return LIB
 
 

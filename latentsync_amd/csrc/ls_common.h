@@ -8,17 +8,8 @@
 
 #include "../../include/ls_hip.h"
 
-// A/B switches read from the environment exist only in the diagnostics build
-// (LS_DIAG_KERNELS, LS_DIAG_BUILD=1): in the default library no dispatch decision and no
-// weight layout depends on the environment -- tuning goes through ls_set_tuning.
-static inline const char* ls_env(const char* name) {
-#ifdef LS_DIAG_KERNELS
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
+// No dispatch decision and no weight layout depends on the environment: the library never
+// reads it, and tuning goes through ls_set_tuning.
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -152,13 +143,9 @@ __device__ __forceinline__ void glds16(const void* src, uint4* lds_dst) {
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-// LDS image of one operand tile: rows of BK bf16, 16-B chunks XOR-swizzled so
+// LDS image of one operand tile: rows of 64 bf16, 16-B chunks XOR-swizzled so
 // the 16-lane groups of a ds_read_b128 fragment read hit distinct bank slots.
-template <int BK>
-__device__ __forceinline__ int swz_bk(int row, int c) {
-  if (BK == 64) return row * 8 + (c ^ ((row >> 1) & 7));
-  return row * 4 + (c ^ ((-(row >> 2)) & 3));
-}
+__device__ __forceinline__ int swz64(int row, int c) { return row * 8 + (c ^ ((row >> 1) & 7)); }
 
 __device__ __forceinline__ void load8f(const float* __restrict__ p, float* d) {
   const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);

@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(512, 1) ff_fused_kernel(FFArgs a) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
     auto frag = [&](int s, int t) {
-      return __builtin_bit_cast(bf16x8, cur[(s >> 1) * 512 + swz_bk<64>(t * 16 + l16, (s & 1) * 4 + lg)]);
+      return __builtin_bit_cast(bf16x8, cur[(s >> 1) * 512 + swz64(t * 16 + l16, (s & 1) * 4 + lg)]);
     };
     // W1 fragments PD1 k-steps ahead, the first PD2 W2 fragments issued under GEMM1 (an
     // LDS read one MFMA ahead left each W2 MFMA waiting out the read's latency)
@@ -236,13 +236,14 @@ struct FFChainArgs {
   float eps;          // the LayerNorm's eps
 };
 
-// FMR = 16-row fragments per wave: 1 -> 8 waves of 16 rows (two per SIMD, <= 256 registers);
-// 2 -> 4 waves of 32 rows, one per SIMD (up to 512 registers, the accumulators in AGPRs):
-// every W fragment read from LDS then feeds two MFMAs -- at one fragment per MFMA the
-// FeedForward's fragment reads alone fill the LDS array (1 KB per 16-cycle MFMA per SIMD =
-// 256 B/clk/CU), which had left it at 0.34 of the MFMA peak.
-template <int C, int I, int FMR>
-__global__ void __launch_bounds__(512 / FMR, 1) ff_chain_kernel(FFChainArgs a) {
+// FMR = 16-row fragments per wave: 8 waves of 16 rows (two per SIMD, <= 256 registers).  At one
+// fragment per MFMA the FeedForward's W fragment reads alone fill the LDS array (1 KB per
+// 16-cycle MFMA per SIMD = 256 B/clk/CU), which leaves it at 0.34 of the MFMA peak; the form with
+// 4 waves of 32 rows (FMR 2, every fragment feeding two MFMAs) measured slower all the same
+// (DESIGN.md section 3).
+template <int C, int I>
+__global__ void __launch_bounds__(512, 1) ff_chain_kernel(FFChainArgs a) {
+  constexpr int FMR = 1;
   constexpr int NW = 8 / FMR;             // waves per block (128 rows)
   constexpr int NT = 64 * NW;
   constexpr int KT = C / 32;              // k-steps of every C-wide contraction
@@ -260,7 +261,7 @@ __global__ void __launch_bounds__(512 / FMR, 1) ff_chain_kernel(FFChainArgs a) {
   constexpr int RG = NT >= C ? 4 : 2;     // row groups of the column-sum pass
   static_assert(STAGE % W2IMG == 0 && KPS >= 1 && WIMG % NT == 0, "ff_chain stage layout");
   static_assert(2 * STAGE * 16 >= 128 * ZP * 2 + RG * (C / 4) * 8 * 4, "ff_chain epilogue LDS");
-  static_assert(C == 320 && I == 1280 && (FMR == 1 || FMR == 2), "ff_chain shape");
+  static_assert(C == 320 && I == 1280, "ff_chain shape");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];  // [2][STAGE], then b1 (2I fp32)
   float* b1s = (float*)(lds + 2 * STAGE);
 
@@ -428,175 +429,61 @@ __global__ void __launch_bounds__(512 / FMR, 1) ff_chain_kernel(FFChainArgs a) {
   }
 
   // ---- phase B: the FeedForward ----
-  // GELU of the chunk's 32 inner columns from the GEMM1 accumulators (biases from LDS)
-  auto gelu_val = [&](f32x4 (&ac)[FMR][4], int c, int f, int hh, int r) __attribute__((always_inline)) {
-    const float* bb = b1s + c * 64 + 32 * hh + 4 * lg;
-    return (__bf16)((ac[f][2 * hh][r] + bb[r]) * gelu_erf(ac[f][2 * hh + 1][r] + bb[16 + r]));
-  };
-  if constexpr (FMR == 2) {
-    // One wave per SIMD, software-pipelined: iteration c runs GEMM1 of chunk c + 1 with the
-    // GELUs of chunk c between its MFMAs, then GEMM2 of chunk c -- a lone wave would
-    // otherwise wait out every MFMA -> GELU -> MFMA dependency.  W1 of chunk c sits in W1
-    // slot c & 1 (the first WIMG of stage c & 1), W2 of chunk c in W2 slot c & 1: W1 runs
-    // one chunk ahead of W2, so at barrier T(c) W1(c + 2) refills the W1 slot GEMM1(c) left and
-    // W2(c + 1) the W2 slot GEMM2(c - 1) left.  (Phase A's last barrier issued W1(0) + W2(0).)
-    auto issue_w1 = [&](int c) __attribute__((always_inline)) {
-      uint4* dst = lds + (c & 1) * STAGE;
+  for (int c = 0; c < NCH; ++c) {
+    const uint4* cur = top(NA + c);
+    // (the GEGLU biases are added after GEMM1: loaded into the accumulators before it, their
+    // LDS latency stood in front of the first MFMA -- 2623-2644 vs 2950-2970 us per call,
+    // profiles/r06n_chain_variants.txt)
+    f32x4 acc[FMR][4];
+    const float* bb = b1s + c * 64 + 4 * lg;
 #pragma unroll
-      for (int p = 0; p < PW1; ++p) {
-        const int q = p * NT + tid, r = (q >> 3) & 63, pc = q & 7;
-        const int lc = pc ^ ((r >> 1) & 7);
-        glds16(a.w1 + (long)(c * 64 + r) * C + (q >> 9) * 64 + lc * 8, dst + p * NT + wid * 64);
+    for (int f = 0; f < FMR; ++f)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc[f][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    auto frag = [&](int s, int t) {
+      return __builtin_bit_cast(bf16x8, cur[(s >> 1) * 512 + swz64(t * 16 + l16, (s & 1) * 4 + lg)]);
+    };
+    const uint4* w2 = cur + WIMG;
+    bf16x8 wf[PD1][4];
+#pragma unroll
+    for (int p = 0; p < PD1; ++p)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) wf[p][t] = frag(p, t);
+    uint4 w2q[PD2];
+#pragma unroll
+    for (int s = 0; s < KT; ++s) {
+      const int sl = s % PD1;
+      bf16x8 cw[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) cw[t] = wf[sl][t];
+      if (s + PD1 < KT) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) wf[sl][t] = frag(s + PD1, t);
+      } else if (s + PD1 - KT < PD2) {
+        w2q[s + PD1 - KT] = w2[((s + PD1 - KT) * 16 + l16) * 4 + p2];
       }
-    };
-    auto issue_w2 = [&](int c) __attribute__((always_inline)) {
-      uint4* dst = lds + (c & 1) * STAGE + WIMG;
-      for (int u = wid; u < UW2; u += NW) glds16(a.w2 + ((long)c * W2IMG + u * 64 + lane) * 8, dst + u * 64);
-    };
-    auto bar = [&]() __attribute__((always_inline)) {
-      wait_vm<0>();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    };
-    // GEMM1 of chunk cn into nx; with GL the GELUs of chunk cn - 1 (from cu) between its k-steps
-    auto gemm1 = [&](int cn, f32x4 (&nx)[FMR][4], f32x4 (&cu)[FMR][4], bf16x8 (&gv)[FMR], auto gl_tag)
-        __attribute__((always_inline)) {
-      constexpr bool GL = decltype(gl_tag)::value;
-      const uint4* cur = lds + (cn & 1) * STAGE;
-      auto frag = [&](int s, int t) {
-        return __builtin_bit_cast(bf16x8, cur[(s >> 1) * 512 + swz_bk<64>(t * 16 + l16, (s & 1) * 4 + lg)]);
-      };
 #pragma unroll
-      for (int f = 0; f < FMR; ++f)
+      for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int t = 0; t < 4; ++t) nx[f][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      bf16x8 wf[PD1][4];
+        for (int f = 0; f < FMR; ++f) acc[f][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cw[t], ar[f][s], acc[f][t], 0, 0, 0);
+    }
 #pragma unroll
-      for (int p = 0; p < PD1; ++p)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) wf[p][t] = frag(p, t);
-#pragma unroll
-      for (int s = 0; s < KT; ++s) {
-        const int sl = s % PD1;
-        bf16x8 cw[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) cw[t] = wf[sl][t];
-        if (s + PD1 < KT) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) wf[sl][t] = frag(s + PD1, t);
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int f = 0; f < FMR; ++f) nx[f][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cw[t], ar[f][s], nx[f][t], 0, 0, 0);
-        if constexpr (GL) {  // two of the 16 GELUs (f, hh, r) per k-step
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const int v = 2 * s + u;
-            if (v < 8 * FMR) gv[v >> 3][v & 7] = gelu_val(cu, cn - 1, v >> 3, (v >> 2) & 1, v & 3);
-          }
-        }
-      }
-    };
-    auto gemm2 = [&](int c, bf16x8 (&gv)[FMR]) __attribute__((always_inline)) {
-      const uint4* w2 = lds + (c & 1) * STAGE + WIMG;
-      uint4 w2q[PD2];
-#pragma unroll
-      for (int q = 0; q < PD2; ++q) w2q[q] = w2[(q * 16 + l16) * 4 + p2];
-#pragma unroll
-      for (int t = 0; t < NT2; ++t) {
-        const bf16x8 wv = __builtin_bit_cast(bf16x8, w2q[t % PD2]);
-        if (t + PD2 < NT2) w2q[t % PD2] = w2[((t + PD2) * 16 + l16) * 4 + p2];
-#pragma unroll
-        for (int f = 0; f < FMR; ++f) out[f][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv, gv[f], out[f][t], 0, 0, 0);
-      }
-    };
-    f32x4 accA[FMR][4], accB[FMR][4];
+    for (int q = PD1; q < PD2; ++q) w2q[q] = w2[(q * 16 + l16) * 4 + p2];
     bf16x8 gv[FMR];
-    bar();  // T(-1): W1(0), W2(0) landed; phase A's stages are free
-    issue_w1(1);
-    gemm1(0, accA, accB, gv, std::false_type{});
-    // iteration c: T(c) (W1(c + 1), W2(c) landed), issue W1(c + 2), W2(c + 1),
-    // GEMM1(c + 1) with GELU(c), GEMM2(c)
-    auto iter = [&](int c, f32x4 (&cu)[FMR][4], f32x4 (&nx)[FMR][4]) __attribute__((always_inline)) {
-      bar();
-      if (c + 2 < NCH) issue_w1(c + 2);
-      if (c + 1 < NCH) issue_w2(c + 1);
-      if (c + 1 < NCH) {
-        gemm1(c + 1, nx, cu, gv, std::true_type{});
-      } else {
 #pragma unroll
-        for (int v = 0; v < 8 * FMR; ++v) gv[v >> 3][v & 7] = gelu_val(cu, c, v >> 3, (v >> 2) & 1, v & 3);
+    for (int f = 0; f < FMR; ++f)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        gv[f][r] = (__bf16)((acc[f][0][r] + bb[r]) * gelu_erf(acc[f][1][r] + bb[16 + r]));
+        gv[f][4 + r] = (__bf16)((acc[f][2][r] + bb[32 + r]) * gelu_erf(acc[f][3][r] + bb[48 + r]));
       }
-      gemm2(c, gv);
-    };
-    static_assert(NCH % 2 == 0, "ff_chain: an even chunk count");
-    for (int c = 0; c < NCH; c += 2) {
-      iter(c, accA, accB);
-      iter(c + 1, accB, accA);
+#pragma unroll
+    for (int t = 0; t < NT2; ++t) {
+      const bf16x8 wv = __builtin_bit_cast(bf16x8, w2q[t % PD2]);
+      if (t + PD2 < NT2) w2q[t % PD2] = w2[((t + PD2) * 16 + l16) * 4 + p2];
+#pragma unroll
+      for (int f = 0; f < FMR; ++f) out[f][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv, gv[f], out[f][t], 0, 0, 0);
     }
-    // phase C's first stage into stage 0 once every wave is done with the FeedForward's slots
-    __syncthreads();
-    issue(NA + NCH, (NA + NCH) & 1);
-  } else {
-    for (int c = 0; c < NCH; ++c) {
-      const uint4* cur = top(NA + c);
-      // (the GEGLU biases are added after GEMM1: loaded into the accumulators before it, their
-      // LDS latency stood in front of the first MFMA -- 2623-2644 vs 2950-2970 us per call,
-      // profiles/r06n_chain_variants.txt)
-      f32x4 acc[FMR][4];
-      const float* bb = b1s + c * 64 + 4 * lg;
-  #pragma unroll
-      for (int f = 0; f < FMR; ++f)
-  #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[f][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      auto frag = [&](int s, int t) {
-        return __builtin_bit_cast(bf16x8, cur[(s >> 1) * 512 + swz_bk<64>(t * 16 + l16, (s & 1) * 4 + lg)]);
-      };
-      const uint4* w2 = cur + WIMG;
-      bf16x8 wf[PD1][4];
-  #pragma unroll
-      for (int p = 0; p < PD1; ++p)
-  #pragma unroll
-        for (int t = 0; t < 4; ++t) wf[p][t] = frag(p, t);
-      uint4 w2q[PD2];
-  #pragma unroll
-      for (int s = 0; s < KT; ++s) {
-        const int sl = s % PD1;
-        bf16x8 cw[4];
-  #pragma unroll
-        for (int t = 0; t < 4; ++t) cw[t] = wf[sl][t];
-        if (s + PD1 < KT) {
-  #pragma unroll
-          for (int t = 0; t < 4; ++t) wf[sl][t] = frag(s + PD1, t);
-        } else if (s + PD1 - KT < PD2) {
-          w2q[s + PD1 - KT] = w2[((s + PD1 - KT) * 16 + l16) * 4 + p2];
-        }
-  #pragma unroll
-        for (int t = 0; t < 4; ++t)
-  #pragma unroll
-          for (int f = 0; f < FMR; ++f) acc[f][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cw[t], ar[f][s], acc[f][t], 0, 0, 0);
-      }
-  #pragma unroll
-      for (int q = PD1; q < PD2; ++q) w2q[q] = w2[(q * 16 + l16) * 4 + p2];
-      bf16x8 gv[FMR];
-  #pragma unroll
-      for (int f = 0; f < FMR; ++f)
-  #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          gv[f][r] = (__bf16)((acc[f][0][r] + bb[r]) * gelu_erf(acc[f][1][r] + bb[16 + r]));
-          gv[f][4 + r] = (__bf16)((acc[f][2][r] + bb[32 + r]) * gelu_erf(acc[f][3][r] + bb[48 + r]));
-        }
-  #pragma unroll
-      for (int t = 0; t < NT2; ++t) {
-        const bf16x8 wv = __builtin_bit_cast(bf16x8, w2q[t % PD2]);
-        if (t + PD2 < NT2) w2q[t % PD2] = w2[((t + PD2) * 16 + l16) * 4 + p2];
-  #pragma unroll
-        for (int f = 0; f < FMR; ++f) out[f][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv, gv[f], out[f][t], 0, 0, 0);
-      }
-    }
-
   }
 
   // ---- phase C: z = y Wp^T + bp + xb ----
@@ -660,205 +547,10 @@ __global__ void __launch_bounds__(512 / FMR, 1) ff_chain_kernel(FFChainArgs a) {
   }
 }
 
-#ifdef LS_DIAG_KERNELS  // measured and rejected: diagnostics build only
-// ff_pair_kernel (round 5, measured and rejected: 2630 vs 2460 us per call, step +3 ms,
-// profiles/r05g_ff.txt, r05g_step_ab.txt -- the exchange barrier lines every wave up mid-chunk, and the
-// two waves of a SIMD then run their GEMM1 / GELU / GEMM2 phases in step instead of beside
-// each other): the same FeedForward with each W fragment read from LDS feeding TWO MFMAs.  ff_fused_kernel's waves own 16 rows, so every 1-KB W1 / W2 fragment it reads
-// serves one 16x16x32 MFMA: 480 KB of LDS reads per chunk and CU against 1920 MFMA cycles
-// per SIMD, and with the fragment-read -> MFMA dependency neither the matrix pipe (38 %
-// busy) nor the LDS (40 %) is kept full (PMC, profiles/r05d_ff_pmc.txt).  Here a PAIR of
-// waves owns 32 rows (two 16-row fragments, A in registers for both: 80 VGPRs) and splits
-// the work by columns:
-//   * GEMM1: wave h of the pair computes the h / g tiles of inner columns 16 h .. 16 h + 15
-//     of the chunk (W1 tiles 2h, 2h + 1) for both row fragments: 20 fragment reads, 40 MFMAs;
-//   * GEGLU -> 4 bf16 per lane and row fragment: inner columns 16 h + 4 lg .. + 3;
-//   * the pair exchanges them through LDS (8 B per lane and row fragment), so each wave
-//     holds GEMM2's full 32-wide B operand -- k-slots 4 lg .. + 3 from wave 0 and 16 + 4 lg
-//     .. + 3 from wave 1, the order pack_ff_w2 already puts the W2 columns in;
-//   * GEMM2: wave h accumulates output columns 160 h .. 160 h + 159 (10 tiles) for both row
-//     fragments: 10 fragment reads, 20 MFMAs.
-// 0.5 KB of LDS reads per MFMA instead of 1, the same MFMAs, GELUs and W DMA per row.  The
-// exchange's barrier is also where W1 of chunk c + 2 is issued into the stage just read (as
-// the W1 images of the stage just read).
-template <int C, int I, int PD1 = 2, int PD2 = 6>
-__global__ void __launch_bounds__(512, 1) ff_pair_kernel(FFArgs a) {
-  constexpr int KT = C / 32;              // GEMM1 k-steps
-  constexpr int NCH = I / 32;             // inner chunks
-  constexpr int WIMG = 64 * (C / 64) * 8; // uint4: W1 chunk, C/64 images of [64 rows][8 pieces]
-  constexpr int W2IMG = C * 4;            // uint4: W2 chunk, [C rows][4 pieces]
-  constexpr int STAGE = WIMG + W2IMG;
-  constexpr int NT2 = C / 32;             // output tiles per wave (half of C / 16)
-  constexpr int PW1 = WIMG / 512;         // W1 pieces per thread per chunk
-  constexpr int UW2 = W2IMG / 64;         // W2 wave-instructions per chunk
-  static_assert(WIMG % 512 == 0 && W2IMG % 64 == 0 && C % 64 == 0 && I % 32 == 0, "ff_pair shape");
-  static_assert(PD1 >= 1 && PD1 <= KT && PD2 >= PD1 && PD2 <= NT2, "prefetch depths");
-  extern __shared__ __attribute__((aligned(16))) uint4 lds[];  // [2][STAGE], b1 (2I fp32), exchange
-  float* b1s = (float*)(lds + 2 * STAGE);
-  uint2* xch = (uint2*)(b1s + 2 * I);    // [4 pairs][2 halves][2 row fragments][64 lanes]
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int l16 = lane & 15, lg = lane >> 4;
-  const int pr = wid >> 1, h = wid & 1;  // pair, half
-  const long row0 = (long)blockIdx.x * 128 + pr * 32 + l16;  // row of fragment 0 (fragment 1: + 16)
-
-  for (int i = tid; i < 2 * I / 4; i += 512) ((float4*)b1s)[i] = ((const float4*)a.b1)[i];
-
-  auto issue_w1 = [&](int c, int st) {
-    uint4* dst = lds + st * STAGE;
-#pragma unroll
-    for (int p = 0; p < PW1; ++p) {
-      const int q = p * 512 + tid, r = (q >> 3) & 63, pc = q & 7;
-      const int lc = pc ^ ((r >> 1) & 7);
-      glds16(a.w1 + (long)(c * 64 + r) * C + p * 64 + lc * 8, dst + p * 512 + wid * 64);
-    }
-  };
-  auto issue_w2 = [&](int c, int st) {
-    uint4* dst = lds + st * STAGE;
-    for (int u = wid; u < UW2; u += 8) glds16(a.w2 + ((long)c * W2IMG + u * 64 + lane) * 8, dst + WIMG + u * 64);
-  };
-  issue_w1(0, 0);
-  issue_w2(0, 0);
-
-  // A rows of both fragments -> registers, LayerNorm in place
-  bf16x8 ar[2][KT];
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    const long row = row0 + 16 * f;
-    const bool live = row < a.M;
-    const u16* src = a.x + (live ? row : 0) * a.ldx + lg * 8;
-#pragma unroll
-    for (int s = 0; s < KT; ++s)
-      ar[f][s] = live ? *(const bf16x8*)(src + s * 32) : __builtin_bit_cast(bf16x8, make_uint4(0, 0, 0, 0));
-    const float2 mr = live ? *(const float2*)(a.ln_mr + 2 * row) : make_float2(0.f, 0.f);
-    const float rstd = mr.y, nmr = -mr.x * mr.y;
-#pragma unroll
-    for (int s = 0; s < KT; ++s) {
-      bf16x8 v = ar[f][s];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = (__bf16)fmaf((float)v[e], rstd, nmr);
-      ar[f][s] = v;
-    }
-  }
-  if (NCH > 1) issue_w1(1, 1);  // W1 runs a half chunk ahead of W2: refilled at the exchange barrier
-
-  f32x4 out[NT2][2];
-#pragma unroll
-  for (int t = 0; t < NT2; ++t) out[t][0] = out[t][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int p2 = lg ^ (((l16 >> 3) & 1) << 1);  // this lane's physical W2 piece
-  uint2* const xmine = xch + ((pr * 2 + h) * 2) * 64 + lane;
-  const uint2* const xpart = xch + ((pr * 2 + (h ^ 1)) * 2) * 64 + lane;
-
-  for (int c = 0; c < NCH; ++c) {
-    if (c + 1 < NCH) wait_vm<PW1>();  // W1 + W2 of chunk c landed; W1 of c + 1 may fly
-    else wait_vm<0>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // everyone's; the other stage's W2 (chunk c - 1) is no longer read
-    asm volatile("" ::: "memory");
-    if (c + 1 < NCH) issue_w2(c + 1, (c + 1) & 1);
-    const uint4* cur = lds + (c & 1) * STAGE;
-
-    // GEMM1: tiles 2h (h) and 2h + 1 (g) of the chunk, both row fragments
-    f32x4 acc[2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) acc[t][0] = acc[t][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    auto frag = [&](int s, int t) {
-      return __builtin_bit_cast(bf16x8, cur[(s >> 1) * 512 + swz_bk<64>((2 * h + t) * 16 + l16, (s & 1) * 4 + lg)]);
-    };
-    const uint4* w2 = cur + WIMG + (size_t)(h * NT2 * 16) * 4;  // this wave's 160 output rows of W2
-    bf16x8 wf[PD1][2];
-#pragma unroll
-    for (int q = 0; q < PD1; ++q)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) wf[q][t] = frag(q, t);
-    uint4 w2q[PD2];
-#pragma unroll
-    for (int s = 0; s < KT; ++s) {
-      const int sl = s % PD1;
-      const bf16x8 c0 = wf[sl][0], c1 = wf[sl][1];
-      if (s + PD1 < KT) {
-        wf[sl][0] = frag(s + PD1, 0);
-        wf[sl][1] = frag(s + PD1, 1);
-      } else if (s + PD1 - KT < PD2) {
-        w2q[s + PD1 - KT] = w2[((s + PD1 - KT) * 16 + l16) * 4 + p2];
-      }
-#pragma unroll
-      for (int f = 0; f < 2; ++f) {
-        acc[0][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c0, ar[f][s], acc[0][f], 0, 0, 0);
-        acc[1][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c1, ar[f][s], acc[1][f], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int q = PD1; q < PD2; ++q) w2q[q] = w2[(q * 16 + l16) * 4 + p2];
-    // GEGLU of inner columns 16 h + 4 lg .. + 3 -> this wave's half of the B operand
-    const float* bb = b1s + c * 64 + 32 * h + 4 * lg;
-    const float4 bh = *(const float4*)(bb), bg = *(const float4*)(bb + 16);
-    const float hb[4] = {bh.x, bh.y, bh.z, bh.w}, gb[4] = {bg.x, bg.y, bg.z, bg.w};
-    uint2 mine[2];
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      float g4[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) g4[r] = (acc[0][f][r] + hb[r]) * gelu_erf(acc[1][f][r] + gb[r]);
-      mine[f] = make_uint2(pack2(g4[0], g4[1]), pack2(g4[2], g4[3]));
-      xmine[f * 64] = mine[f];
-    }
-    // the pair's exchange; every wave's GEMM1 reads of this stage's W1 images have retired too,
-    // so they are refilled with chunk c + 2
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (c + 2 < NCH) issue_w1(c + 2, c & 1);
-    bf16x8 gv[2];
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      const uint2 other = xpart[f * 64];
-      const uint4 q = h == 0 ? make_uint4(mine[f].x, mine[f].y, other.x, other.y)
-                             : make_uint4(other.x, other.y, mine[f].x, mine[f].y);
-      gv[f] = __builtin_bit_cast(bf16x8, q);
-    }
-    // GEMM2: out^T[160 h + 16 t + 4 lg + r][row] += W2[160 h + 16 t + l16][chunk k-slots] . G^T
-#pragma unroll
-    for (int t = 0; t < NT2; ++t) {
-      const bf16x8 wv = __builtin_bit_cast(bf16x8, w2q[t % PD2]);
-      if (t + PD2 < NT2) w2q[t % PD2] = w2[((t + PD2) * 16 + l16) * 4 + p2];
-      out[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv, gv[0], out[t][0], 0, 0, 0);
-      out[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv, gv[1], out[t][1], 0, 0, 0);
-    }
-  }
-
-  // y = out + b2 + x for this wave's 160 columns of both row fragments
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    const long row = row0 + 16 * f;
-    if (row >= a.M) continue;
-    const u16* xr = a.x + row * a.ldx;
-    u16* yr = a.y + row * a.ldy;
-#pragma unroll
-    for (int t = 0; t < NT2; ++t) {
-      const int col = C / 2 * h + 16 * t + 4 * lg;
-      const float4 b = *(const float4*)(a.b2 + col);
-      const uint2 rs = *(const uint2*)(xr + col);
-      const float o0 = out[t][f][0] + b.x + __uint_as_float(rs.x << 16);
-      const float o1 = out[t][f][1] + b.y + __uint_as_float(rs.x & 0xffff0000u);
-      const float o2 = out[t][f][2] + b.z + __uint_as_float(rs.y << 16);
-      const float o3 = out[t][f][3] + b.w + __uint_as_float(rs.y & 0xffff0000u);
-      *(uint2*)(yr + col) = make_uint2(pack2(o0, o1), pack2(o2, o3));
-    }
-  }
-}
-
-#endif  // LS_DIAG_KERNELS
 
 }  // namespace ls
 
 using namespace ls;
-
-// rows per wave of ls_ff_chain: 16 (1, the default) or, in the diagnostics build, 32 (2) --
-// ls_set_tuning key 17.  Measured and rejected (profiles/r06c_kernel.txt, same box, M = 786432):
-// 32 rows, one wave per SIMD 3058 us straight / 5120 us software-pipelined (AGPR traffic and
-// scratch in the chunk loop) against 2695 us at 16 rows
-int g_ff_chain_fmr = 1;
 
 extern "C" int ls_ff_chain(const ls_ff_chain_desc* d, void* stream) {
   if (!d || !d->o || !d->wo || !d->bo || !d->h1 || !d->w1 || !d->b1 || !d->w2 || !d->b2 || !d->wp || !d->bp ||
@@ -881,15 +573,8 @@ extern "C" int ls_ff_chain(const ls_ff_chain_desc* d, void* stream) {
   a.M = d->M; a.ldo = d->ldo; a.ldh = d->ldh; a.ldxb = d->ldxb; a.ldz = d->ldz; a.eps = d->eps;
   constexpr int C = 320, I = 1280;
   const size_t shm = (size_t)2 * (64 * (C / 64) * 8 + C * 4) * 16 + 2 * I * sizeof(float);
-#ifdef LS_DIAG_KERNELS
-  if (g_ff_chain_fmr == 2) {
-    LS_SET_MAX_DYN_SHM((ff_chain_kernel<C, I, 2>), (int)shm);
-    ff_chain_kernel<C, I, 2><<<(unsigned)(d->M / 128), 256, shm, (hipStream_t)stream>>>(a);
-    return check_launch("ff_chain_kernel");
-  }
-#endif
-  LS_SET_MAX_DYN_SHM((ff_chain_kernel<C, I, 1>), (int)shm);
-  ff_chain_kernel<C, I, 1><<<(unsigned)(d->M / 128), 512, shm, (hipStream_t)stream>>>(a);
+  LS_SET_MAX_DYN_SHM((ff_chain_kernel<C, I>), (int)shm);
+  ff_chain_kernel<C, I><<<(unsigned)(d->M / 128), 512, shm, (hipStream_t)stream>>>(a);
   return check_launch("ff_chain_kernel");
 }
 
@@ -907,15 +592,6 @@ extern "C" int ls_feedforward(const ls_ff_desc* d, void* stream) {
   a.x = (const u16*)d->x; a.ln_mr = d->ln_rowstats; a.w1 = (const u16*)d->w1; a.b1 = d->b1;
   a.w2 = (const u16*)d->w2; a.b2 = d->b2; a.y = (u16*)d->y; a.M = d->M; a.ldx = d->ldx; a.ldy = d->ldy;
   constexpr int C = 320, I = 1280;
-#ifdef LS_DIAG_KERNELS
-  static const bool pair = ls_env("LS_FF_PAIR") != nullptr && atoi(ls_env("LS_FF_PAIR")) != 0;  // A/B switch
-  if (pair) {
-    const size_t shm = (size_t)2 * (64 * (C / 64) * 8 + C * 4) * 16 + 2 * I * sizeof(float) + 4 * 2 * 2 * 64 * 8;
-    LS_SET_MAX_DYN_SHM((ff_pair_kernel<C, I>), (int)shm);
-    ff_pair_kernel<C, I><<<(unsigned)((d->M + 127) / 128), 512, shm, (hipStream_t)stream>>>(a);
-    return check_launch("ff_pair_kernel");
-  }
-#endif
   const size_t shm = (size_t)2 * (64 * (C / 64) * 8 + C * 4) * 16 + 2 * I * sizeof(float);
   LS_SET_MAX_DYN_SHM((ff_fused_kernel<C, I>), (int)shm);
   ff_fused_kernel<C, I><<<(unsigned)((d->M + 127) / 128), 512, shm, (hipStream_t)stream>>>(a);

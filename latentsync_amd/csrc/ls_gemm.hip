@@ -62,8 +62,7 @@ __device__ __forceinline__ void tile_of(const ConvArgs& a, int bid, int& tm, int
 // a pixel chunk's 3x3 neighbourhood in 9 back-to-back K-tiles and the re-reads hit L2
 // (tap-major, the 9 re-reads of a pixel were Cin / 64 K-tiles apart and, with 64 blocks
 // per XCD streaming operands in between, missed: profiles/r03e_pmc_per_kernel.txt).
-// Returns the tap and sets c0 = the K-tile's first input channel (k0 = a 64-aligned or,
-// for BK 32, 32-aligned K offset).
+// Returns the tap and sets c0 = the K-tile's first input channel (k0 = a 64-aligned K offset).
 __device__ __forceinline__ int tap_of(const ConvArgs& a, int k0, int& c0) {
   if (a.phase) {  // k = (ci / 64) * 256 + t * 64 + ci % 64: 3x3 tap (py + t / 2, px + t % 2)
     const int t = (k0 >> 6) & 3, ph = a.phase - 1;
@@ -764,20 +763,20 @@ __global__ void __launch_bounds__(256) conv_gemm_kernel(ConvArgs a) {
 __device__ uint4 ls_zero_page[2];
 
 
-template <int KS, bool TAPU, int BK = 64>
+template <int KS, bool TAPU>
 __device__ __forceinline__ const void* a_src(const ConvArgs& a, int kt, int c, int m, const RowGeo& g) {
   // branch-free: compute the candidate address, then select it or the zero page
   int cg, tap = 0;
   bool ok;
   if (KS == 1) {
-    cg = kt * BK + c * 8;
+    cg = kt * 64 + c * 8;
     ok = (m < a.M) & (cg < a.Cin);
   } else if (TAPU) {
-    tap = tap_of(a, kt * BK, cg);
+    tap = tap_of(a, kt * 64, cg);
     cg += c * 8;
     ok = true;
   } else {
-    const int kc = kt * (BK / 8) + c;
+    const int kc = kt * 8 + c;
     tap = kc / a.CC;
     cg = (kc - tap * a.CC) * 8;
     ok = tap < 9;
@@ -985,8 +984,9 @@ struct BufDma {
 // pixels before the tile's first input image, so every window's top-left pixel has
 // a non-negative offset; the tap's (kh W + kw) pixel shift and channel offset go in
 // soffset, taps outside the image select an offset past the descriptor (zeros).
-template <int BM, int BN, int WM, int WN, int KS, bool TAPU, int NST, int BK, int EPI, bool BUF = false>
+template <int BM, int BN, int WM, int WN, int KS, bool TAPU, int EPI, bool BUF = false>
 __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_dma_kernel(ConvArgs a) {
+  constexpr int NST = 2, BK = 64;                     // LDS stages, K-tile depth (what ships)
   constexpr int NT = WM * WN * 64;                    // 256 (4 waves) or 512 (8 waves, 256-row tiles)
   constexpr int WTM = BM / WM, WTN = BN / WN;
   constexpr int FM = WTM / 16, FN = WTN / 16;
@@ -1022,7 +1022,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_dma_kernel(ConvArgs a)
     const int row = q / CPR;
     const int pc = q % CPR;
     arow[p] = m0 + row;
-    ach[p] = swz_bk<BK>(row, pc) - row * CPR;  // logical chunk stored at physical chunk pc (involution)
+    ach[p] = swz64(row, pc) - row * CPR;  // logical chunk stored at physical chunk pc (involution)
     if (KS == 3) {
       const int m = m0 + row;
       const int hw = a.Ho * a.Wo;
@@ -1040,9 +1040,9 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_dma_kernel(ConvArgs a)
     const int q = (wid * BI + p) * 64 + lane;
     const int row = q / CPR;
     brow[p] = n0 + row;
-    bch[p] = swz_bk<BK>(row, q % CPR) - row * CPR;
+    bch[p] = swz64(row, q % CPR) - row * CPR;
   }
-  static_assert(!BUF || (BK == 64 && (KS == 1 || TAPU)), "buffer DMA: BK 64, 1x1 or tap-major 3x3");
+  static_assert(!BUF || KS == 1 || TAPU, "buffer DMA: 1x1 or tap-major 3x3");
   BufDma<BM, BN, AI, BI, KS> bd;  // BUF (dead code otherwise)
   if constexpr (BUF) {
     int ar[AI], br[BI];
@@ -1060,7 +1060,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_dma_kernel(ConvArgs a)
     } else {
 #pragma unroll
       for (int p = 0; p < AI; ++p)
-        glds16(a_src<KS, TAPU, BK>(a, kt, ach[p], arow[p], geo[p]), base + (wid * AI + p) * 64);
+        glds16(a_src<KS, TAPU>(a, kt, ach[p], arow[p], geo[p]), base + (wid * AI + p) * 64);
 #pragma unroll
       for (int p = 0; p < BI; ++p) {
         const void* src = brow[p] < a.N ? (const void*)(a.w + (long)brow[p] * a.K + kt * BK + bch[p] * 8)
@@ -1080,13 +1080,11 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_dma_kernel(ConvArgs a)
 #pragma unroll
   for (int t = 0; t < NST - 1; ++t)
     if (kt0 + t < kt1 && do_dma) issue(kt0 + t, t);
-  // ILV (2-stage buffer-descriptor path): the next K-tile's DMA is issued after this
-  // K-tile's barrier, its wave-instructions spread between the MFMAs (sched_group_barrier)
-  // instead of one burst before the wait -- an LDS-DMA instruction costs ~60 issue cycles
-  // among MFMAs but 100-185 in a burst beside the fragment reads (MI355X_MICROARCH.md).  Its
-  // stage was last read in K-tile kt - 1, whose trailing barrier every wave has passed.
-  constexpr bool ILV = false;  // (A/B: BUF && NST == 2)
-  constexpr bool ILV_SGB = false;  // explicit interleave (sched_group_barrier): see DESIGN
+  // ILV: the next K-tile's DMA issued after this K-tile's barrier instead of in one burst before
+  // the wait; measured and rejected.  The constant and its dead second
+  // issue() call site stay: without them the compiler orders two v_mov of the EPI_ANY instances'
+  // epilogue differently, and the shipped instructions are held fixed.
+  constexpr bool ILV = false;
   int stage = 0;
   // the plain epilogue's first-pass side inputs (residual / LayerNorm rows), loaded during
   // the last K-tile so their HBM latency hides under its MFMAs
@@ -1098,9 +1096,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_dma_kernel(ConvArgs a)
     constexpr bool IS = decltype(is_tag)::value;
     if (!ILV && kt + NST - 1 < kt1 && do_dma) issue(kt + NST - 1, (stage + NST - 1) % NST);
     const int ahead = ILV ? 0 : min(NST - 1, kt1 - 1 - kt);
-    if (NST >= 4 && ahead >= 3) wait_vm<3 * L>();
-    else if (NST >= 3 && ahead >= 2) wait_vm<2 * L>();
-    else if (ahead >= 1) wait_vm<L>();
+    if (ahead >= 1) wait_vm<L>();
     else wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -1114,10 +1110,10 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_dma_kernel(ConvArgs a)
       const int c = ks * 4 + (lane >> 4);
 #pragma unroll
       for (int i = 0; i < FM; ++i)
-        af[ks][i] = __builtin_bit_cast(bf16x8, cur[swz_bk<BK>(wm * WTM + i * 16 + (lane & 15), c)]);
+        af[ks][i] = __builtin_bit_cast(bf16x8, cur[swz64(wm * WTM + i * 16 + (lane & 15), c)]);
 #pragma unroll
       for (int j = 0; j < FN; ++j)
-        bfr[ks][j] = __builtin_bit_cast(bf16x8, cur[BM * CPR + swz_bk<BK>(wn * WTN + j * 16 + (lane & 15), c)]);
+        bfr[ks][j] = __builtin_bit_cast(bf16x8, cur[BM * CPR + swz64(wn * WTN + j * 16 + (lane & 15), c)]);
     }
     if (ILV && IS && kt + 1 < kt1 && do_dma) issue(kt + 1, stage ^ 1);
 #ifdef LS_GEMM_ABLATE
@@ -1132,18 +1128,8 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_dma_kernel(ConvArgs a)
           for (int j = 0; j < FN; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks][i], bfr[ks][j], acc[i][j], 0, 0, 0);
     }
-    if constexpr (ILV && IS && ILV_SGB) {  // fragment reads first, then L x (one DMA, MFMAs), the rest
-      constexpr int NMF = KSTEPS * FM * FN, PER = NMF / (L + 1) > 0 ? NMF / (L + 1) : 1;
-      __builtin_amdgcn_sched_group_barrier(0x100, KSTEPS * (FM + FN), 0);
-#pragma unroll
-      for (int r = 0; r < L; ++r) {
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, NMF - L * PER > 0 ? NMF - L * PER : 0, 0);
-    }
 #ifdef LS_GEMM_ABLATE
-    else if (a.ablate & 32) {
+    if (a.ablate & 32) {
       acc[0][0][0] += (float)af[0][0][0] + (float)bfr[0][0][0];
     }
 #endif
@@ -1174,226 +1160,6 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_dma_kernel(ConvArgs a)
   store_tile<BM, BN, WM, WN, EPI>(a, acc, (float*)lds, m0, n0, z);
 }
 
-#ifdef LS_DIAG_KERNELS  // measured and rejected: diagnostics build only
-// Register-staged variant of conv_gemm_dma_kernel's BUF path (A/B switch LS_GEMM_RS=1):
-// the same buffer-descriptor offsets, but each 16-B operand piece goes through a VGPR
-// (buffer_load_dwordx4, then ds_write_b128 into the slot the LDS-DMA would have written)
-// instead of buffer_load ... lds.  MI355X_MICROARCH.md prices an LDS-DMA wave-instruction
-// at ~60 issue cycles beside MFMAs; a VMEM load + a 16-B LDS store are a fraction of that,
-// at the cost of 4 VGPRs per piece held across the K-tile's MFMAs.  Loads of K-tile t+1
-// are issued right after the barrier of K-tile t and stored after its MFMAs.
-template <int BM, int BN, int WM, int WN, int KS, int EPI>
-__global__ void __launch_bounds__(WM * WN * 64) conv_gemm_rs_kernel(ConvArgs a) {
-  constexpr int NT = WM * WN * 64;
-  constexpr int WTM = BM / WM, WTN = BN / WN;
-  constexpr int FM = WTM / 16, FN = WTN / 16;
-  constexpr int CPR = 8;
-  constexpr int AI = BM * CPR / NT, BI = BN * CPR / NT;
-  static_assert((BM * CPR) % NT == 0 && (BN * CPR) % NT == 0, "operand pieces must divide over the threads");
-  constexpr int STAGE = (BM + BN) * CPR;
-  extern __shared__ __attribute__((aligned(16))) uint4 lds_dyn[];
-  uint4* lds = lds_dyn;
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid / WN, wn = wid % WN;
-  const int nt = a.ntm * a.ntn;
-  int bid = xcd_remap(blockIdx.x, nt);
-  int tm, tn;
-  tile_of(a, bid, tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int kt1 = a.ktiles;
-
-  int ar[AI], ach[AI], br[BI], bch[BI];
-#pragma unroll
-  for (int p = 0; p < AI; ++p) {
-    const int q = (wid * AI + p) * 64 + lane;
-    const int row = q / CPR;
-    ar[p] = row;
-    ach[p] = swz_bk<64>(row, q % CPR) - row * CPR;
-  }
-#pragma unroll
-  for (int p = 0; p < BI; ++p) {
-    const int q = (wid * BI + p) * 64 + lane;
-    const int row = q / CPR;
-    br[p] = row;
-    bch[p] = swz_bk<64>(row, q % CPR) - row * CPR;
-  }
-  BufDma<BM, BN, AI, BI, KS> bd;
-  bd.init(a, m0, n0, ar, ach, br, bch);
-  uint4 ra[AI], rb[BI];
-  auto gload = [&](int kt) {
-    const auto k = bd.next(a, kt);
-    const bool ups = KS == 3 && a.upsample;
-#pragma unroll
-    for (int p = 0; p < AI; ++p) ra[p] = bd.reg_a(p, k, ups);
-#pragma unroll
-    for (int p = 0; p < BI; ++p) rb[p] = bd.reg_b(p, k);
-  };
-  auto lstore = [&](int stage) {
-    uint4* base = lds + stage * STAGE;
-#pragma unroll
-    for (int p = 0; p < AI; ++p) base[(wid * AI + p) * 64 + lane] = ra[p];
-#pragma unroll
-    for (int p = 0; p < BI; ++p) base[BM * CPR + (wid * BI + p) * 64 + lane] = rb[p];
-  };
-
-  f32x4 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  gload(0);
-  lstore(0);
-  int stage = 0;
-  for (int kt = 0; kt < kt1; ++kt) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    const bool more = kt + 1 < kt1;
-    if (more) gload(kt + 1);
-    const uint4* cur = lds + stage * STAGE;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int c = ks * 4 + (lane >> 4);
-      bf16x8 af[FM], bfr[FN];
-#pragma unroll
-      for (int i = 0; i < FM; ++i) af[i] = __builtin_bit_cast(bf16x8, cur[swz_bk<64>(wm * WTM + i * 16 + (lane & 15), c)]);
-#pragma unroll
-      for (int j = 0; j < FN; ++j)
-        bfr[j] = __builtin_bit_cast(bf16x8, cur[BM * CPR + swz_bk<64>(wn * WTN + j * 16 + (lane & 15), c)]);
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
-    if (more) lstore(stage ^ 1);  // stage ^ 1 was read in K-tile kt - 1, before this barrier
-    stage ^= 1;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  store_tile<BM, BN, WM, WN, EPI>(a, acc, (float*)lds, m0, n0, 0);
-}
-
-// 1x1 GEMM with the A operand straight into registers (A/B switch LS_GEMM_AREG / tuning key
-// 14): a lane's A fragment of a 32-wide k-step is 8 consecutive channels of one row -- 16
-// contiguous bytes of the NHWC activation -- so it is one buffer_load_dwordx4 into the MFMA
-// operand registers, no LDS.  Only B (the weights) goes through an LDS-DMA ring (3 stages,
-// 20 KB each at BN 160): per K-tile a wave issues BN/32 LDS-DMA instructions instead of
-// (BM + BN)/32, the rest of the operand traffic being plain vector loads (each A element is
-// read by the WN waves of its row band, from L1 / L2).  A of K-tile kt + 1 is loaded during
-// K-tile kt (two register sets, the K loop unrolled by 2 so the sets are static).
-template <int BM, int BN, int WM, int WN, int EPI>
-__global__ void __launch_bounds__(WM * WN * 64) conv_gemm_areg_kernel(ConvArgs a) {
-  constexpr int NT = WM * WN * 64;
-  constexpr int WTM = BM / WM, WTN = BN / WN;
-  constexpr int FM = WTM / 16, FN = WTN / 16;
-  constexpr int BI = BN * 8 / NT;
-  static_assert((BN * 8) % NT == 0, "B pieces must divide over the threads");
-  constexpr int STAGE = BN * 8;  // uint4 per B stage
-  extern __shared__ __attribute__((aligned(16))) uint4 lds_dyn[];
-  uint4* lds = lds_dyn;
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int l16 = lane & 15, lg = lane >> 4;
-  const int wm = wid / WN, wn = wid % WN;
-  const int nt = a.ntm * a.ntn;
-  int bid = xcd_remap(blockIdx.x, nt);
-  int tm, tn;
-  tile_of(a, bid, tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int kt1 = a.K / 64;
-  const long cap = 0x7FFFFFFFL;
-
-  // A: rows past M read zeros (descriptor size); concat K-tiles from x2 (host: C1 % 64 == 0)
-  const i32x4 rs_a1 = buffer_rsrc(a.x1 + (long)m0 * a.ld1, (uint32_t)min((long)(a.M - m0) * a.ld1 * 2, cap));
-  const i32x4 rs_a2 =
-      a.C2 ? buffer_rsrc(a.x2 + (long)m0 * a.ld2, (uint32_t)min((long)(a.M - m0) * a.ld2 * 2, cap)) : rs_a1;
-  int avo1[FM], avo2[FM];
-#pragma unroll
-  for (int i = 0; i < FM; ++i) {
-    const int r = wm * WTM + i * 16 + l16;
-    avo1[i] = (r * a.ld1 + lg * 8) * 2;
-    avo2[i] = (r * a.ld2 + lg * 8) * 2;
-  }
-  // B: pieces lane-linear per wave, 16-B chunks XOR-swizzled as in the LDS-DMA kernels
-  const i32x4 rs_b = buffer_rsrc(a.w + (long)n0 * a.K, (uint32_t)min((long)(a.N - n0) * a.K * 2, cap));
-  int bvo[BI];
-#pragma unroll
-  for (int p = 0; p < BI; ++p) {
-    const int q = (wid * BI + p) * 64 + lane, row = q / 8;
-    const int lc = swz_bk<64>(row, q % 8) - row * 8;  // logical chunk stored at physical chunk q % 8
-    bvo[p] = (row * a.K + lc * 8) * 2;
-  }
-  const int wid_u = __builtin_amdgcn_readfirstlane(wid);
-  auto issue_b = [&](int kt) {
-    uint4* base = lds + (kt % 3) * STAGE;
-#pragma unroll
-    for (int p = 0; p < BI; ++p)
-      ls_raw_buffer_load_lds(rs_b, (__attribute__((address_space(3))) void*)(base + (wid_u * BI + p) * 64), 16, bvo[p],
-                             kt * 128, 0, 0);
-  };
-  bf16x8 ar[2][2][FM];  // [register set][k-step][fragment]
-  auto load_a = [&](int kt, bf16x8 (&r)[2][FM]) {
-    const bool two = a.C2 && kt * 64 >= a.C1;
-    const int soff = (two ? kt * 64 - a.C1 : kt * 64) * 2;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-        r[ks][i] = __builtin_bit_cast(bf16x8, ls_raw_buffer_load_v4(two ? rs_a2 : rs_a1, two ? avo2[i] : avo1[i],
-                                                                    soff + ks * 64, 0));
-  };
-
-  f32x4 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  issue_b(0);
-  if (kt1 > 1) issue_b(1);
-  load_a(0, ar[0]);
-  // K-tile kt from register set CUR; B of kt lands in stage kt % 3 (issued two K-tiles ahead)
-  auto body = [&](int kt, auto cur_tag) {
-    constexpr int CUR = decltype(cur_tag)::value;
-    if (kt + 2 < kt1) issue_b(kt + 2);
-    if (kt + 1 < kt1) load_a(kt + 1, ar[CUR ^ 1]);
-    // B(kt) and A(kt) landed: the VMEM instructions younger than A(kt) are B(kt + 2) and A(kt + 1)
-    if (kt + 2 < kt1) wait_vm<BI + 2 * FM>();
-    else if (kt + 1 < kt1) wait_vm<2 * FM>();
-    else wait_vm<0>();
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    const uint4* cur = lds + (kt % 3) * STAGE;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 bfr[FN];
-#pragma unroll
-      for (int j = 0; j < FN; ++j)
-        bfr[j] = __builtin_bit_cast(bf16x8, cur[swz_bk<64>(wn * WTN + j * 16 + l16, ks * 4 + lg)]);
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ar[CUR][ks][i], bfr[j], acc[i][j], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // stage kt % 3 free for B(kt + 3)
-    asm volatile("" ::: "memory");
-  };
-  int kt = 0;
-  for (; kt + 1 < kt1; kt += 2) {
-    body(kt, std::integral_constant<int, 0>{});
-    body(kt + 1, std::integral_constant<int, 1>{});
-  }
-  if (kt < kt1) body(kt, std::integral_constant<int, 0>{});
-  store_tile<BM, BN, WM, WN, EPI>(a, acc, (float*)lds, m0, n0, 0);
-}
-
-#endif  // LS_DIAG_KERNELS
 
 // 256-row tile, 8 waves (2 M x 4 N), each wave 128 x BN/4 (FM = 8 fragments of
 // 16 rows x FN of 16 cols): 1.5x the MFMAs per LDS fragment read of the 4-wave
@@ -1433,7 +1199,7 @@ __global__ void __launch_bounds__(512) conv_gemm_big_kernel(ConvArgs a) {
     const int q = (wid * AI + p) * 64 + lane;
     const int row = q / CPR;
     arow[p] = m0 + row;
-    ach[p] = swz_bk<BK>(row, q % CPR) - row * CPR;
+    ach[p] = swz64(row, q % CPR) - row * CPR;
     if (KS == 3) {
       const int m = m0 + row;
       const int hw = a.Ho * a.Wo;
@@ -1451,7 +1217,7 @@ __global__ void __launch_bounds__(512) conv_gemm_big_kernel(ConvArgs a) {
     const int q = (wid * BI + p) * 64 + lane;
     const int row = q / CPR;
     brow[p] = n0 + row;
-    bch[p] = swz_bk<BK>(row, q % CPR) - row * CPR;
+    bch[p] = swz64(row, q % CPR) - row * CPR;
   }
   static_assert(!BUF || KS == 1 || TAPU, "buffer DMA: 1x1 or tap-major 3x3");
   BufDma<BM, BN, AI, BI, KS> bd;  // BUF (dead code otherwise)
@@ -1472,7 +1238,7 @@ __global__ void __launch_bounds__(512) conv_gemm_big_kernel(ConvArgs a) {
     }
 #pragma unroll
     for (int p = 0; p < AI; ++p)
-      glds16(a_src<KS, TAPU, BK>(a, kt, ach[p], arow[p], geo[p]), base + (wid * AI + p) * 64);
+      glds16(a_src<KS, TAPU>(a, kt, ach[p], arow[p], geo[p]), base + (wid * AI + p) * 64);
 #pragma unroll
     for (int p = 0; p < BI; ++p) {
       const void* src = brow[p] < a.N ? (const void*)(a.w + (long)brow[p] * a.K + kt * BK + bch[p] * 8)
@@ -1501,10 +1267,10 @@ __global__ void __launch_bounds__(512) conv_gemm_big_kernel(ConvArgs a) {
       const int c = ks * 4 + (lane >> 4);
 #pragma unroll
       for (int j = 0; j < FN; ++j)
-        bfr[ks][j] = __builtin_bit_cast(bf16x8, cur[BM * CPR + swz_bk<BK>(wn * WTN + j * 16 + (lane & 15), c)]);
+        bfr[ks][j] = __builtin_bit_cast(bf16x8, cur[BM * CPR + swz64(wn * WTN + j * 16 + (lane & 15), c)]);
 #pragma unroll
       for (int i = 0; i < FH; ++i)
-        af[ks][i] = __builtin_bit_cast(bf16x8, cur[swz_bk<BK>(wm * WTM + i * 16 + (lane & 15), c)]);
+        af[ks][i] = __builtin_bit_cast(bf16x8, cur[swz64(wm * WTM + i * 16 + (lane & 15), c)]);
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -1515,7 +1281,7 @@ __global__ void __launch_bounds__(512) conv_gemm_big_kernel(ConvArgs a) {
           const int c = ks * 4 + (lane >> 4);
 #pragma unroll
           for (int i = 0; i < FH; ++i)
-            an[ks][i] = __builtin_bit_cast(bf16x8, cur[swz_bk<BK>(wm * WTM + (FH + i) * 16 + (lane & 15), c)]);
+            an[ks][i] = __builtin_bit_cast(bf16x8, cur[swz64(wm * WTM + (FH + i) * 16 + (lane & 15), c)]);
         }
       }
       __builtin_amdgcn_s_setprio(1);
@@ -1543,294 +1309,6 @@ __global__ void __launch_bounds__(512) conv_gemm_big_kernel(ConvArgs a) {
   store_tile<BM, BN, WM, WN, EPI>(a, acc, (float*)lds, m0, n0, z);
 }
 
-#ifdef LS_DIAG_KERNELS  // measured and rejected: diagnostics build only
-// 256 x 256 x 64 tile, 8 waves (2 M x 4 N, 128 x 64 per wave), phased schedule
-// (after the guide's 8-phase template): each K-tile runs as 4 phases, one per
-// 64 x 32 quadrant of the wave tile (16 MFMAs).  A phase issues the fragment
-// reads it needs (A quadrant rows and/or B quadrant cols), ONE half-tile of
-// operand DMA (2 glds per thread; half-tiles A0 A1 B0 B1 = 128 rows x 64 k)
-// D = 5 half-tiles ahead, barrier, waits for its reads (they overlap the
-// barrier), MFMAs at raised priority, barrier.  The DMA for tile t+1 is retired
-// by a counted vmcnt(2) in phase 3 of tile t, so operand loads span barriers and
-// never drain in the main loop.  Hazards (g = 4t + phase): half g+5 overwrites
-// half g-3 -- A0(t) last read by row 0 at 4t+2, re-staged at 4t+3 after that
-// row retired the reads in its own phase 4t+2; A1 at 4t+4, B0 at 4t+5, B1 at
-// 4t+6 (B last read at 4t+1).  Row 1 runs one barrier behind row 0.
-template <int KS, bool TAPU>
-__global__ void __launch_bounds__(512) conv_gemm_p8_kernel(ConvArgs a) {
-  constexpr int BM = 256, BN = 256, BK = 64, CPR = 8;
-  constexpr int HALF = 128 * CPR;         // uint4 per half-tile (16 KB)
-  constexpr int BUF = 4 * HALF;           // A0 A1 B0 B1
-  constexpr int D = 5;                    // half-tiles of DMA issued ahead
-  extern __shared__ __attribute__((aligned(16))) uint4 lds_dyn[];
-  uint4* lds = lds_dyn;
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wr = wid >> 2, wc = wid & 3;
-  const int nt = a.ntm * a.ntn;
-  int bid = xcd_remap(blockIdx.x, nt * a.split);
-  const int z = bid / nt;
-  bid -= z * nt;
-  int tm, tn;
-  tile_of(a, bid, tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int kt0 = z * a.kt_per_split;
-  const int nk = min(a.ktiles, kt0 + a.kt_per_split) - kt0;
-  const int nhalf = 4 * nk;
-
-  // per-thread DMA geometry: instruction i (0, 1) of each half covers rows (wid*2+i)*8 + lane/8
-  int arow[4], ach[4], brow[4], bch[4];
-  RowGeo geo[4];
-#pragma unroll
-  for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int q = (wid * 2 + i) * 64 + lane;
-      const int row = q / CPR, pc = q % CPR;
-      const int lc = swz_bk<BK>(row, pc) - row * CPR;
-      const int p = hh * 2 + i;
-      arow[p] = m0 + hh * 128 + row;
-      ach[p] = lc;
-      brow[p] = n0 + hh * 128 + row;
-      bch[p] = lc;
-      if (KS == 3) {
-        const int m = arow[p];
-        const int hw = a.Ho * a.Wo;
-        const int n = m / hw, r = m - n * hw;
-        const int yo = r / a.Wo, xo = r - yo * a.Wo;
-        geo[p].pb = n * a.H * a.W;
-        geo[p].yb = (m < a.M) ? (a.upsample ? yo - a.pad : yo * a.stride - a.pad) : -(1 << 28);
-        geo[p].xb = a.upsample ? xo - a.pad : xo * a.stride - a.pad;
-      } else {
-        geo[p].pb = 0; geo[p].yb = 0; geo[p].xb = 0;
-      }
-    }
-  // issue half-tile s (tile s/4, half s%4: A0 A1 B0 B1) into its buffer
-  auto issue_half = [&](int s) {
-    if (s >= nhalf) return;
-    const int t = s >> 2, h = s & 3;
-    const int kt = kt0 + t;
-    uint4* dst = lds + (t & 1) * BUF + h * HALF + wid * 2 * 64;
-    if (h < 2) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int p = (h & 1) * 2 + i;
-        glds16(a_src<KS, TAPU, BK>(a, kt, ach[p], arow[p], geo[p]), dst + i * 64);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int p = (h & 1) * 2 + i;
-        const void* src = brow[p] < a.N ? (const void*)(a.w + (long)brow[p] * a.K + kt * BK + bch[p] * 8)
-                                        : (const void*)ls_zero_page;
-        glds16(src, dst + i * 64);
-      }
-    }
-  };
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  // prologue: half-tiles 0 .. D-1 in flight, tile 0 landed
-#pragma unroll
-  for (int s = 0; s < D; ++s) issue_half(s);
-  if (nhalf > 4) wait_vm<2>(); else wait_vm<0>();  // tile 0 (halves 0..3) landed, half 4 in flight
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-
-  // ping-pong: the two wave rows (one wave of each per SIMD) run one barrier
-  // apart, so one wave's MFMA section overlaps the other's load section
-  if (wr == 1) __builtin_amdgcn_s_barrier();
-  bf16x8 af[2][4], b0[2][2], b1[2][2];
-  const int arow_w = wr * 128;            // this wave's rows inside the A tile (= its A half)
-  const int bh = wc >> 1, bcol = (wc & 1) * 64;  // B half + column offset inside it
-  for (int t = 0; t < nk; ++t) {
-    const uint4* buf = lds + (t & 1) * BUF;
-    const uint4* Ah = buf + wr * HALF;
-    const uint4* Bh = buf + (2 + bh) * HALF;
-#pragma unroll
-    for (int ph = 0; ph < 4; ++ph) {
-      const int qm = (ph == 0 || ph == 1) ? 0 : 1;
-      const int qn = (ph == 0 || ph == 3) ? 0 : 1;
-      // fragment reads this phase needs
-      if (ph == 0 || ph == 3) {
-        if (ph == 0) {
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-              b0[ks][j] = __builtin_bit_cast(
-                  bf16x8, Bh[swz_bk<BK>(bcol + j * 16 + (lane & 15), ks * 4 + (lane >> 4))]);
-        }
-      } else if (ph == 1) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            b1[ks][j] = __builtin_bit_cast(
-                bf16x8, Bh[swz_bk<BK>(bcol + 32 + j * 16 + (lane & 15), ks * 4 + (lane >> 4))]);
-      }
-      if (ph == 0 || ph == 2) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            af[ks][i] = __builtin_bit_cast(
-                bf16x8, Ah[swz_bk<BK>(qm * 64 + i * 16 + (lane & 15), ks * 4 + (lane >> 4))]);
-      }
-      (void)arow_w;
-      // one half-tile of DMA, D ahead
-      issue_half(4 * t + ph + D);
-      if (ph == 3) {  // retire tile t+1 (issued up to 4t+8 now; t+1 ends at 4t+7)
-        if (4 * t + 3 + D < nhalf) wait_vm<2>();
-        else wait_vm<0>();
-      }
-      __builtin_amdgcn_s_barrier();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this phase's reads, overlapped with the barrier
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const bf16x8 bv = qn == 0 ? b0[ks][j] : b1[ks][j];
-            acc[qm * 4 + i][qn * 2 + j] =
-                __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks][i], bv, acc[qm * 4 + i][qn * 2 + j], 0, 0, 0);
-          }
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    }
-  }
-  if (wr == 0) __builtin_amdgcn_s_barrier();  // re-align the rows before the LDS is reused
-  asm volatile("" ::: "memory");
-  store_tile<BM, BN, 2, 4>(a, acc, (float*)lds, m0, n0, z);
-}
-
-// 256 x 256 tile, 8 waves (128 x 64 per wave), BK = 32 with a 4-stage LDS ring
-// (4 x 32 KB): the DMA runs three K-tiles ahead of the MFMAs behind a counted
-// vmcnt, one raw barrier per K-tile.  For operand streams that come from the
-// Infinity Cache / HBM rather than L2 (the 2-stage BK = 64 ring can only cover
-// one K-tile of latency).
-template <int KS, bool TAPU>
-__global__ void __launch_bounds__(512) conv_gemm_big4_kernel(ConvArgs a) {
-  constexpr int BM = 256, BN = 256, BK = 32, NST = 4, WM = 2, WN = 4;
-  constexpr int WTM = BM / WM, WTN = BN / WN;
-  constexpr int FM = WTM / 16, FN = WTN / 16, FH = FM / 2;
-  constexpr int CPR = BK / 8;
-  constexpr int AI = BM * CPR / 512, BI = BN * CPR / 512;  // 2 + 2 glds per thread per stage
-  constexpr int L = AI + BI;
-  constexpr int STAGE = (BM + BN) * CPR;
-  extern __shared__ __attribute__((aligned(16))) uint4 lds_dyn[];
-  uint4* lds = lds_dyn;
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid / WN, wn = wid % WN;
-  const int nt = a.ntm * a.ntn;
-  int bid = xcd_remap(blockIdx.x, nt * a.split);
-  const int z = bid / nt;
-  bid -= z * nt;
-  int tm, tn;
-  tile_of(a, bid, tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int kps = a.kt_per_split * 2;  // 32-wide K-tiles per split
-  const int kt0 = z * kps;
-  const int kt1 = min(a.ktiles * 2, kt0 + kps);
-
-  int arow[AI], ach[AI], brow[BI], bch[BI];
-  RowGeo geo[AI];
-#pragma unroll
-  for (int p = 0; p < AI; ++p) {
-    const int q = (wid * AI + p) * 64 + lane;
-    const int row = q / CPR;
-    arow[p] = m0 + row;
-    ach[p] = swz_bk<BK>(row, q % CPR) - row * CPR;
-    if (KS == 3) {
-      const int m = m0 + row;
-      const int hw = a.Ho * a.Wo;
-      const int n = m / hw, r = m - n * hw;
-      const int yo = r / a.Wo, xo = r - yo * a.Wo;
-      geo[p].pb = n * a.H * a.W;
-      geo[p].yb = (m < a.M) ? (a.upsample ? yo - a.pad : yo * a.stride - a.pad) : -(1 << 28);
-      geo[p].xb = a.upsample ? xo - a.pad : xo * a.stride - a.pad;
-    } else {
-      geo[p].pb = 0; geo[p].yb = 0; geo[p].xb = 0;
-    }
-  }
-#pragma unroll
-  for (int p = 0; p < BI; ++p) {
-    const int q = (wid * BI + p) * 64 + lane;
-    const int row = q / CPR;
-    brow[p] = n0 + row;
-    bch[p] = swz_bk<BK>(row, q % CPR) - row * CPR;
-  }
-  auto issue = [&](int kt, int stage) {
-    uint4* base = lds + stage * STAGE;
-#pragma unroll
-    for (int p = 0; p < AI; ++p)
-      glds16(a_src<KS, TAPU, BK>(a, kt, ach[p], arow[p], geo[p]), base + (wid * AI + p) * 64);
-#pragma unroll
-    for (int p = 0; p < BI; ++p) {
-      const void* src = brow[p] < a.N ? (const void*)(a.w + (long)brow[p] * a.K + kt * BK + bch[p] * 8)
-                                      : (const void*)ls_zero_page;
-      glds16(src, base + BM * CPR + (wid * BI + p) * 64);
-    }
-  };
-
-  f32x4 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-#pragma unroll
-  for (int t = 0; t < NST - 1; ++t)
-    if (kt0 + t < kt1) issue(kt0 + t, t);
-  int stage = 0;
-  for (int kt = kt0; kt < kt1; ++kt) {
-    // tile kt landed for this wave: later tiles (up to 2) may stay in flight
-    const int ahead = min(NST - 2, kt1 - 1 - kt);
-    if (ahead >= 2) wait_vm<2 * L>();
-    else if (ahead == 1) wait_vm<L>();
-    else wait_vm<0>();
-    __builtin_amdgcn_s_barrier();  // everyone's tile kt landed; stage of kt-1 free
-    asm volatile("" ::: "memory");
-    if (kt + NST - 1 < kt1) issue(kt + NST - 1, (stage + NST - 1) & (NST - 1));
-    const uint4* cur = lds + stage * STAGE;
-    const int c = lane >> 4;
-    bf16x8 bfr[FN], a0[FH], a1[FH];
-#pragma unroll
-    for (int j = 0; j < FN; ++j)
-      bfr[j] = __builtin_bit_cast(bf16x8, cur[BM * CPR + swz_bk<BK>(wn * WTN + j * 16 + (lane & 15), c)]);
-#pragma unroll
-    for (int i = 0; i < FH; ++i) a0[i] = __builtin_bit_cast(bf16x8, cur[swz_bk<BK>(wm * WTM + i * 16 + (lane & 15), c)]);
-#pragma unroll
-    for (int i = 0; i < FH; ++i)
-      a1[i] = __builtin_bit_cast(bf16x8, cur[swz_bk<BK>(wm * WTM + (FH + i) * 16 + (lane & 15), c)]);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < FH; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[i], bfr[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < FH; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j)
-        acc[FH + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[i], bfr[j], acc[FH + i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    stage = (stage + 1) & (NST - 1);
-  }
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  store_tile<BM, BN, WM, WN>(a, acc, (float*)lds, m0, n0, z);
-}
-
-#endif  // LS_DIAG_KERNELS
 
 // split-K reduction + epilogue: one thread per 8 output columns
 __global__ void splitk_reduce_kernel(ConvArgs a) {
@@ -1993,12 +1471,7 @@ __global__ void __launch_bounds__(512) gemm_rowblock_kernel(ConvArgs a) {
   // images, then the chunk's 64 bias, colsum and row-vector values (wave 0).
   // piece q = p * 512 + tid of a chunk's images: image t = q / (8 BN), row (q / 8) % BN, chunk q % 8
   const long rv_base = RV ? rv_row(a, rb * BM) : 0;  // host: rows_per_vec % BM == 0
-#ifdef LS_DIAG_KERNELS  // timing ablations (LS_GEMM_ABLATE): 2 no chunk DMA past the first two, 4 no
-  // stores, 64 no A-row loads (zeros) -- results are garbage; profiles/r05l_ablate.txt
-  const int abl = a.ablate;
-#else
   constexpr int abl = 0;
-#endif
   // W / residual DMA through buffer descriptors (round 6): the per-thread byte offsets are
   // fixed over the chunks, a chunk moves only the uniform soffset, and the LDS destinations
   // are LDS-space addresses -- one s_add to M0 per DMA instead of a 64-bit global address,
@@ -2223,7 +1696,7 @@ __global__ void __launch_bounds__(512) gemm_rowblock_kernel(ConvArgs a) {
       const int ch = (s & 1) * 4 + lg;
 #pragma unroll
       for (int j = 0; j < FN; ++j)
-        bw[j] = __builtin_bit_cast(bf16x8, cur[(s >> 1) * (8 * BN) + swz_bk<64>(j * 16 + l16, ch)]);
+        bw[j] = __builtin_bit_cast(bf16x8, cur[(s >> 1) * (8 * BN) + swz64(j * 16 + l16, ch)]);
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -2627,7 +2100,7 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
       bf16x8 bfr[FN];
 #pragma unroll
       for (int j = 0; j < FN; ++j)
-        bfr[j] = __builtin_bit_cast(bf16x8, wb[swz_bk<64>(wn * WTN + j * 16 + l16, ks * 4 + lg)]);
+        bfr[j] = __builtin_bit_cast(bf16x8, wb[swz64(wn * WTN + j * 16 + l16, ks * 4 + lg)]);
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -2668,18 +2141,13 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
 }
 
 // ---------------------------------------------------------------- host side
-static bool g_force_regstage = ls_env("LS_GEMM_REGSTAGE") != nullptr;
-// A/B switch: 3x3 weights packed tap-major (packing.py reads the same variable)
-static const int g_gemm_gm = ls_env("LS_GEMM_GM") ? atoi(ls_env("LS_GEMM_GM")) : 0;  // A/B switch: tile raster
-static const bool g_gm_shortk = ls_env("LS_GEMM_GM_SHORTK") == nullptr || atoi(ls_env("LS_GEMM_GM_SHORTK")) != 0;
-static int g_force_tile = 0, g_force_split = 0, g_bk = 64;
-// ablation bits (diagnostics; tuning key 4 or LS_GEMM_ABLATE): 1 no MFMA, 2 no operand DMA,
+static bool g_force_regstage = false;  // tuning key 1
+static int g_force_tile = 0, g_force_split = 0;  // tuning keys 2, 3
+// ablation bits (diagnostics; tuning key 4): 1 no MFMA, 2 no operand DMA,
 // 4 no output store, 8 the general epilogue arithmetic even where the short path applies
-static int g_ablate = ls_env("LS_GEMM_ABLATE") ? atoi(ls_env("LS_GEMM_ABLATE")) : 0;
+static int g_ablate = 0;
 
 struct TileCfg { int bm, bn, split; };
-// A/B switch (LS_GEMM_BIG1280=0): the N = 1280 linears back on 128 x 160 tiles
-static bool g_big1280 = ls_env("LS_GEMM_BIG1280") == nullptr || atoi(ls_env("LS_GEMM_BIG1280")) != 0;
 
 // Tile + split-K choice by a small cost model.  A CU runs up to R blocks of a tile
 // at once (LDS-limited: 2 for the 4-wave 128-row tiles, 1 for the 8-wave 256x256);
@@ -2703,9 +2171,7 @@ static TileCfg pick_tile(long M, int N, int ktiles, bool allow_split, bool big_o
       // levels' projections, FF2 and shortcuts, 7-16 % faster than 128x160 on every one of
       // them, profiles/r05c_n1280.txt) or when 160 does not divide N (the VAE's 512); 3x3
       // convs: the cost model decides
-      if (ksize == 1 && ((N % 256 != 0 && N < 1920) || (N < 1280 && N % 160 == 0) ||
-                         (N == 1280 && !g_big1280)))
-        continue;
+      if (ksize == 1 && ((N % 256 != 0 && N < 1920) || (N < 1280 && N % 160 == 0))) continue;
     }
     if (c.bn == 160 && N % 160 != 0) continue;  // the UNet's widths are all multiples of 160
     const long tiles = (long)cdiv(M, c.bm) * cdiv(N, c.bn);
@@ -2726,9 +2192,9 @@ static TileCfg pick_tile(long M, int N, int ktiles, bool allow_split, bool big_o
 }
 
 // ---- row-block GEMM dispatch (gemm_rowblock_kernel)
-static bool g_rowblock = ls_env("LS_GEMM_NO_ROWBLOCK") == nullptr;
-static bool g_rowblock640 = ls_env("LS_GEMM_NO_ROWBLOCK640") == nullptr;
-static bool g_rb640_res = ls_env("LS_GEMM_RB640_RES") != nullptr;  // A/B switch: K = 640 residual GEMMs too
+static bool g_rowblock = true;     // tuning key 6
+static bool g_rowblock640 = true;  // tuning key 7
+static bool g_rb640_res = false;   // tuning key 20: K = 640 residual GEMMs too
 
 static bool rowblock_ok(const ls_conv_desc* d, const ConvArgs& a) {
   if (!g_rowblock || g_force_tile || g_force_regstage || d->ksize != 1 || a.C2) return false;
@@ -2761,8 +2227,8 @@ static void launch_rowblock2(const ConvArgs& a, int grid, hipStream_t s) {
 
 // K = 640 with two 16-row fragments per wave (256-row blocks, half the W-fragment LDS reads
 // per MFMA, 160 A registers): default since r04x (step 215.3 -> 212.2 ms at 48 windows, three
-// same-box alternations); tuning key 15 / LS_RB640_FM2=0: one fragment per wave
-static bool g_rb640_fm2 = ls_env("LS_RB640_FM2") == nullptr || atoi(ls_env("LS_RB640_FM2")) != 0;
+// same-box alternations); tuning key 15 = 0: one fragment per wave
+static bool g_rb640_fm2 = true;
 
 static bool rb640_fm2(int flags);
 
@@ -2848,89 +2314,42 @@ static int epi_kind(const ConvArgs& a) {
   return EPI_ANY;
 }
 
-template <int BM, int BN, int WM, int WN, int KS, bool TAPU, int NST, int BK, int EPI, bool BUF = false>
+template <int BM, int BN, int WM, int WN, int KS, bool TAPU, int EPI, bool BUF = false>
 static void launch_dma1(const ConvArgs& a, int grid, hipStream_t s) {
-  // staging for the epilogue must fit too
-  const size_t shm = std::max<size_t>((size_t)NST * (BM + BN) * (BK / 8) * 16, (size_t)(BM / WM) * (BN + 4) * 4);
-  LS_SET_MAX_DYN_SHM((conv_gemm_dma_kernel<BM, BN, WM, WN, KS, TAPU, NST, BK, EPI, BUF>), (int)shm);
-  conv_gemm_dma_kernel<BM, BN, WM, WN, KS, TAPU, NST, BK, EPI, BUF><<<grid, WM * WN * 64, shm, s>>>(a);
-}
-
-static bool g_no_buf_dma = ls_env("LS_GEMM_GLDS") != nullptr;  // A/B switch: global_load_lds addressing
-#ifdef LS_DIAG_KERNELS  // measured and rejected: diagnostics build only
-static int g_rs = ls_env("LS_GEMM_RS") ? atoi(ls_env("LS_GEMM_RS")) : 0;  // A/B switch: register-staged buffer loads
-
-template <int BM, int BN, int WM, int WN, int KS, int EPI>
-static void launch_rs(const ConvArgs& a, int grid, hipStream_t s) {
+  // two stages of 64-deep K-tiles; staging for the epilogue must fit too
   const size_t shm = std::max<size_t>((size_t)2 * (BM + BN) * 8 * 16, (size_t)(BM / WM) * (BN + 4) * 4);
-  LS_SET_MAX_DYN_SHM((conv_gemm_rs_kernel<BM, BN, WM, WN, KS, EPI>), (int)shm);
-  conv_gemm_rs_kernel<BM, BN, WM, WN, KS, EPI><<<grid, WM * WN * 64, shm, s>>>(a);
+  LS_SET_MAX_DYN_SHM((conv_gemm_dma_kernel<BM, BN, WM, WN, KS, TAPU, EPI, BUF>), (int)shm);
+  conv_gemm_dma_kernel<BM, BN, WM, WN, KS, TAPU, EPI, BUF><<<grid, WM * WN * 64, shm, s>>>(a);
 }
-static bool g_areg = ls_env("LS_GEMM_AREG") ? atoi(ls_env("LS_GEMM_AREG")) != 0 : false;  // A/B switch: 1x1 A in registers
-
-template <int BM, int BN, int WM, int WN, int EPI>
-static void launch_areg(const ConvArgs& a, int grid, hipStream_t s) {
-  const size_t shm = std::max<size_t>((size_t)3 * BN * 8 * 16, (size_t)(BM / WM) * (BN + 4) * 4);
-  LS_SET_MAX_DYN_SHM((conv_gemm_areg_kernel<BM, BN, WM, WN, EPI>), (int)shm);
-  conv_gemm_areg_kernel<BM, BN, WM, WN, EPI><<<grid, WM * WN * 64, shm, s>>>(a);
-}
-#endif  // LS_DIAG_KERNELS
-
-static bool g_no_buf_ups = ls_env("LS_GEMM_UPS_GLDS") != nullptr;  // A/B switch: ... for upsampling convs only
 
 // operand DMA through buffer descriptors: 1x1 with K == Cin, Cin % 64 == 0; tap-major 3x3,
 // stride 1 or 2, pad 0 or 1, or nearest-x2 upsample with pad 1; C1 % 64 == 0 (a K-tile never straddles the
 // concat); byte offsets of a tile's window must fit 31 bits (they do: < 16 MB)
 static bool buf_dma_ok(const ConvArgs& a, int ks) {
-  if (g_no_buf_dma || a.aff_scale) return false;
+  if (a.aff_scale) return false;
   if (ks == 1) return a.Cin % 64 == 0 && a.C1 % 64 == 0 && a.K == a.Cin;
-  if (a.upsample) return !g_no_buf_ups && a.Cin % 64 == 0 && a.C1 % 64 == 0 && a.stride == 1 && a.pad == 1;
+  if (a.upsample) return a.Cin % 64 == 0 && a.C1 % 64 == 0 && a.stride == 1 && a.pad == 1;
   return a.Cin % 64 == 0 && a.C1 % 64 == 0 && (a.stride == 1 || a.stride == 2) && (a.pad == 0 || a.pad == 1);
 }
 
 template <int BM, int BN, int WM, int WN, int KS, bool TAPU>
 static void launch_dma(const ConvArgs& a, int grid, hipStream_t s) {
-  // (BK 32 tuning mode: only tiles whose 16-B operand pieces divide over the threads --
-  // 128 x 160 has 640 B pieces for 256 threads and would leave B rows unloaded)
-#ifdef LS_DIAG_KERNELS
-  if constexpr (BN >= 64 && (BN * 4) % (WM * WN * 64) == 0 && (BM * 4) % (WM * WN * 64) == 0) {
-    if (g_bk == 32) { launch_dma1<BM, BN, WM, WN, KS, TAPU, 4, 32, EPI_ANY>(a, grid, s); return; }
-  }
-#endif
   if constexpr (KS == 1 || TAPU) {
-#ifdef LS_DIAG_KERNELS
-    if constexpr (KS == 1) {
-      if (g_areg && buf_dma_ok(a, 1) && a.split == 1) {
-        switch (epi_kind(a)) {
-          case EPI_PLAIN: launch_areg<BM, BN, WM, WN, EPI_PLAIN>(a, grid, s); return;
-          case EPI_GEGLU: launch_areg<BM, BN, WM, WN, EPI_GEGLU>(a, grid, s); return;
-          default: launch_areg<BM, BN, WM, WN, EPI_ANY>(a, grid, s); return;
-        }
-      }
-    }
-    if (g_rs && buf_dma_ok(a, KS) && a.split == 1) {
-      switch (epi_kind(a)) {
-        case EPI_PLAIN: launch_rs<BM, BN, WM, WN, KS, EPI_PLAIN>(a, grid, s); return;
-        case EPI_GEGLU: launch_rs<BM, BN, WM, WN, KS, EPI_GEGLU>(a, grid, s); return;
-        default: launch_rs<BM, BN, WM, WN, KS, EPI_ANY>(a, grid, s); return;
-      }
-    }
-#endif
     if constexpr (KS == 3 && TAPU) {  // the tiled phase form (tiled_phase_ok: buffer-descriptor DMA)
-      if (a.phase) { launch_dma1<BM, BN, WM, WN, KS, TAPU, 2, 64, EPI_PLAINP, true>(a, grid, s); return; }
+      if (a.phase) { launch_dma1<BM, BN, WM, WN, KS, TAPU, EPI_PLAINP, true>(a, grid, s); return; }
     }
     if (buf_dma_ok(a, KS)) {
       switch (epi_kind(a)) {
-        case EPI_PLAIN: launch_dma1<BM, BN, WM, WN, KS, TAPU, 2, 64, EPI_PLAIN, true>(a, grid, s); return;
-        case EPI_GEGLU: launch_dma1<BM, BN, WM, WN, KS, TAPU, 2, 64, EPI_GEGLU, true>(a, grid, s); return;
-        default: launch_dma1<BM, BN, WM, WN, KS, TAPU, 2, 64, EPI_ANY, true>(a, grid, s); return;
+        case EPI_PLAIN: launch_dma1<BM, BN, WM, WN, KS, TAPU, EPI_PLAIN, true>(a, grid, s); return;
+        case EPI_GEGLU: launch_dma1<BM, BN, WM, WN, KS, TAPU, EPI_GEGLU, true>(a, grid, s); return;
+        default: launch_dma1<BM, BN, WM, WN, KS, TAPU, EPI_ANY, true>(a, grid, s); return;
       }
     }
   }
   switch (epi_kind(a)) {
-    case EPI_PLAIN: launch_dma1<BM, BN, WM, WN, KS, TAPU, 2, 64, EPI_PLAIN>(a, grid, s); break;
-    case EPI_GEGLU: launch_dma1<BM, BN, WM, WN, KS, TAPU, 2, 64, EPI_GEGLU>(a, grid, s); break;
-    default: launch_dma1<BM, BN, WM, WN, KS, TAPU, 2, 64, EPI_ANY>(a, grid, s);
+    case EPI_PLAIN: launch_dma1<BM, BN, WM, WN, KS, TAPU, EPI_PLAIN>(a, grid, s); break;
+    case EPI_GEGLU: launch_dma1<BM, BN, WM, WN, KS, TAPU, EPI_GEGLU>(a, grid, s); break;
+    default: launch_dma1<BM, BN, WM, WN, KS, TAPU, EPI_ANY>(a, grid, s);
   }
 }
 
@@ -2962,22 +2381,6 @@ static void launch_big1(const ConvArgs& a, int grid, hipStream_t s) {
   }
 }
 
-#ifdef LS_DIAG_KERNELS  // measured and rejected: diagnostics build only
-template <int KS, bool TAPU>
-static void launch_big4(const ConvArgs& a, int grid, hipStream_t s) {
-  const size_t shm = std::max<size_t>((size_t)4 * (256 + 256) * 4 * 16, (size_t)128 * (256 + 4) * 4);
-  LS_SET_MAX_DYN_SHM((conv_gemm_big4_kernel<KS, TAPU>), (int)shm);
-  conv_gemm_big4_kernel<KS, TAPU><<<grid, 512, shm, s>>>(a);
-}
-
-template <int KS, bool TAPU>
-static void launch_p8_1(const ConvArgs& a, int grid, hipStream_t s) {
-  const size_t shm = std::max<size_t>((size_t)2 * 4 * 128 * 8 * 16, (size_t)128 * (256 + 4) * 4);
-  LS_SET_MAX_DYN_SHM((conv_gemm_p8_kernel<KS, TAPU>), (int)shm);
-  conv_gemm_p8_kernel<KS, TAPU><<<grid, 512, shm, s>>>(a);
-}
-
-#endif  // LS_DIAG_KERNELS
 
 template <int BN>
 static void launch_big(const ConvArgs& a, int ks, bool tapu, int grid, hipStream_t s) {
@@ -3000,12 +2403,12 @@ static void launch_cfg(const ConvArgs& a, int ks, bool tapu, int grid, hipStream
 }
 
 // ---- halo-tile 3x3 conv dispatch (conv3x3_halo_kernel)
-static bool g_halo = ls_env("LS_HALO") == nullptr || atoi(ls_env("LS_HALO")) != 0;  // A/B switch: LS_HALO=0
+static bool g_halo = true;  // tuning key 8
 // the nearest-x2 upsample convs on the halo kernel too (tuning key 18; off: the tiled gather)
-static bool g_halo_ups = ls_env("LS_HALO_UPS") == nullptr || atoi(ls_env("LS_HALO_UPS")) != 0;
-// A/B switch (tuning key 13): 128-channel tiles where both divide N (3-slot weight ring
-// instead of 2 at BN 160)
-static bool g_halo_bn128 = ls_env("LS_HALO_BN128") != nullptr;
+static bool g_halo_ups = true;
+// tuning key 13: 128-channel tiles where both divide N (3-slot weight ring instead of 2 at
+// BN 160)
+static bool g_halo_bn128 = false;
 
 // the narrow 16-column tile for N <= 16 (tuning key 19; off: the tiled GEMM's 128 x 32 tile)
 static bool g_halo_narrow = true;
@@ -3063,8 +2466,8 @@ static void launch_halo2(const ConvArgs& a, hipStream_t s) {
 // chunks (Cin <= 256), where a block's halo prologue and epilogue are a large share of its
 // time: VAE 128 ch at 256^2 17.67 -> 17.23 ms, 128 -> 256 at 128^2 8.74 -> 8.43 ms, 256 at
 // 128^2 a tie; at Cin 512 (8 chunks) the 2-slot weight ring loses to the 1-block form's 3
-// slots (13.12 -> 13.55 ms at 64^2), profiles/r05k_halo_ab.txt.  A/B switch LS_HALO_TH8=0.
-static bool g_halo_th8 = ls_env("LS_HALO_TH8") == nullptr || atoi(ls_env("LS_HALO_TH8")) != 0;
+// slots (13.12 -> 13.55 ms at 64^2), profiles/r05k_halo_ab.txt.  Tuning key 16 = 0: off.
+static bool g_halo_th8 = true;
 
 template <int TW>
 static void launch_halo1(const ConvArgs& a, hipStream_t s) {
@@ -3108,13 +2511,6 @@ static void launch_halo(const ConvArgs& a, int tw, hipStream_t s) {
   launch_halo1<16>(a, s);
 }
 
-#ifdef LS_DIAG_KERNELS  // measured and rejected: diagnostics build only
-// 256 x 128 tiles (8 waves as 4 x 2, 64 x 64 each) with a 3-stage LDS ring (147 KB) for the
-// short-K linears (K <= 1280, N % 128 == 0): two K-tiles of operand DMA in flight instead of
-// one.  (A/B switch LS_GEMM_T256=0/1; tile id 260.  256 x 160 would leave 2.5 B pieces per thread.)
-static int g_t256 = ls_env("LS_GEMM_T256") ? atoi(ls_env("LS_GEMM_T256")) : 0;
-
-#endif  // LS_DIAG_KERNELS
 
 // The phase form of an upsample conv (upsample == 2) on the tiled kernels, for what the halo
 // kernel does not take (N > 640, images its patches do not divide): per output parity a plain
@@ -3124,7 +2520,7 @@ static int g_t256 = ls_env("LS_GEMM_T256") ? atoi(ls_env("LS_GEMM_T256")) : 0;
 static bool tiled_phase_ok(const ls_conv_desc* d, const ConvArgs& a, const TileCfg& t) {
   const bool vec = (a.N % 8 == 0) && (a.ldy % 8 == 0) && (!a.res || a.ldr % 8 == 0);
   return d->upsample == 2 && vec && !a.y_f32 && a.act == LS_ACT_NONE && !a.rowvec && !a.C2 && !g_force_regstage &&
-         t.bm <= 256 && buf_dma_ok(a, 3);
+         buf_dma_ok(a, 3);
 }
 
 static void to_tiled_phase(ConvArgs& a, const TileCfg& t) {
@@ -3189,28 +2585,23 @@ static int build_args(const ls_conv_desc* d, ConvArgs& a, TileCfg& t, int& split
   t = pick_tile(M, d->N, a.ktiles, d->split_k <= 0 && d->workspace != nullptr && d->upsample != 2,
                 !d->aff_scale && !g_force_regstage && (d->ksize == 1 || Cin % 64 == 0), d->ksize);
   if (g_force_tile) {
-    static const int tb[11][2] = {{0, 0}, {128, 128}, {128, 64}, {64, 64}, {128, 32}, {256, 256}, {256, 128},
-                                  {257, 256}, {258, 256}, {128, 160}, {259, 160}};
+    // (ids 7 and 8 were rejected 256-row variants; ls_set_tuning refuses them)
+    static const int tb[10][2] = {{0, 0}, {128, 128}, {128, 64}, {64, 64}, {128, 32}, {256, 256}, {256, 128},
+                                  {0, 0}, {0, 0}, {128, 160}};
     t.bm = tb[g_force_tile][0]; t.bn = tb[g_force_tile][1]; t.split = g_force_split ? g_force_split : 1;
     // the 256-row kernels have no register-staged form (affine prologue, tuning key 1): such a
     // call runs a 128-row kernel, and the grid below must be the one of the kernel launched
     if (t.bm >= 256 && (d->aff_scale || g_force_regstage)) { t.bm = 128; t.bn = 128; }
   }
-#ifdef LS_DIAG_KERNELS
-  if (g_t256 && !g_force_tile && d->ksize == 1 && a.ktiles <= 20 && d->N % 128 == 0 && !d->aff_scale &&
-      M % 256 == 0 && d->K == Cin && Cin % 64 == 0 && d->C1 % 64 == 0)
-    t = {260, 128, 1};
-#endif
-  a.ntm = cdiv(M, t.bm > 256 ? 256 : t.bm); a.ntn = cdiv(d->N, t.bn);  // 257..260 = 256-row kernel variants
-  // grouped raster (LS_GEMM_GM=g, g row-bands per group): it cuts the wide linears' L2-miss
+  a.ntm = cdiv(M, t.bm); a.ntn = cdiv(d->N, t.bn);
+  // grouped raster (g row-bands per group): it cuts the wide linears' L2-miss
   // fetch (GEGLU W1 at 8x8 3.6 -> 1.3 GB per call) but measured +0.4 ms per 32-window step
   // against the column-fastest order over three alternated same-box rounds
   // (profiles/r03i_locality_sweep.txt), so the default stays column-fastest (gm = 1)
-  a.gm = g_gemm_gm > 0 ? g_gemm_gm : 1;
+  a.gm = 1;
   // round 5: 4 row bands per group for 256x256 1x1 tiles with K <= 1920 (out2 181 -> 173 us,
-  // sc2b -1 %, profiles/r05s_gm_ab.txt; at K = 5120 the grouping loses); A/B switch
-  // LS_GEMM_GM_SHORTK=0
-  if (g_gemm_gm <= 0 && g_gm_shortk && t.bm == 256 && t.bn == 256 && d->ksize == 1 && d->K <= 1920) a.gm = 4;
+  // sc2b -1 %, profiles/r05s_gm_ab.txt; at K = 5120 the grouping loses)
+  if (t.bm == 256 && t.bn == 256 && d->ksize == 1 && d->K <= 1920) a.gm = 4;
   a.gm = std::max(1, std::min(a.gm, a.ntm));
   split = d->upsample == 2 ? 1 : d->split_k > 0 ? d->split_k : t.split;  // (the phase forms have no split-K)
   split = std::min(split, a.ktiles);
@@ -3225,55 +2616,35 @@ static int build_args(const ls_conv_desc* d, ConvArgs& a, TileCfg& t, int& split
 
 using namespace ls;
 
-namespace ls { void attn_set_attn6(bool on); }
-
-extern int g_ff_chain_fmr;  // ls_ff.hip
-
 extern "C" int ls_set_tuning(int32_t key, int32_t value) {
   switch (key) {
     case 18: g_halo_ups = value != 0; return LS_OK;
     case 19: g_halo_narrow = value != 0; return LS_OK;
     case 20: g_rb640_res = value != 0; return LS_OK;
     case 17:
-#ifndef LS_DIAG_KERNELS
-      if (value == 2) return fail(LS_ERR_INVALID, "ls_ff_chain at 32 rows per wave: diagnostics build only");
-#endif
-      if (value != 1 && value != 2) return fail(LS_ERR_INVALID, "ls_ff_chain rows per wave: 1 (16) or 2 (32)");
-      g_ff_chain_fmr = value;
+      // (2, 32 rows per wave, was measured and rejected: DESIGN.md section 3)
+      if (value != 1) return fail(LS_ERR_INVALID, "ls_ff_chain rows per wave: 1 (16) only");
       return LS_OK;
     case 1: g_force_regstage = value != 0; return LS_OK;
     case 2:
-#ifndef LS_DIAG_KERNELS
-      if (value == 7 || value == 8) return fail(LS_ERR_INVALID, "tile ids 7 / 8: diagnostics build only");
-#endif
-      if (value < 0 || value > 9) return fail(LS_ERR_INVALID, "tile id 0..9");
+      if (value < 0 || value > 9 || value == 7 || value == 8) return fail(LS_ERR_INVALID, "tile id 0..6 or 9");
       g_force_tile = value;
       return LS_OK;
     case 3: g_force_split = value; return LS_OK;
     case 4: g_ablate = value; return LS_OK;
-#ifdef LS_DIAG_KERNELS
-    case 5: if (value != 32 && value != 64) return fail(LS_ERR_INVALID, "BK 32 or 64"); g_bk = value; return LS_OK;
-#endif
     case 6: g_rowblock = value != 0; return LS_OK;
     case 7: g_rowblock640 = value != 0; return LS_OK;
     case 8: g_halo = value != 0; return LS_OK;
     case 12:  // (the padded-row halo image is gone since the compact image, round 5)
-      if (!value) return fail(LS_ERR_INVALID, "LS_HALO_RP=0 (padded halo rows) no longer exists");
+      if (!value) return fail(LS_ERR_INVALID, "key 12 = 0 (padded halo rows) no longer exists");
       return LS_OK;
     case 13: g_halo_bn128 = value != 0; return LS_OK;
     case 15: g_rb640_fm2 = value != 0; return LS_OK;
     case 16: g_halo_th8 = value != 0; return LS_OK;
     case 9:
-#ifndef LS_DIAG_KERNELS
-      if (value) return fail(LS_ERR_INVALID, "attn6: diagnostics build only");
-#endif
-      attn_set_attn6(value != 0);
+      // (the attn6 kernel was measured and rejected: DESIGN.md section 3)
+      if (value) return fail(LS_ERR_INVALID, "attention variant: 0 only");
       return LS_OK;
-#ifdef LS_DIAG_KERNELS
-    case 10: g_t256 = value; return LS_OK;
-    case 11: g_rs = value; return LS_OK;
-    case 14: g_areg = value != 0; return LS_OK;
-#endif
     default: return fail(LS_ERR_INVALID, "ls_set_tuning: unknown key");
   }
 }
@@ -3288,10 +2659,10 @@ static int occ(K kern, int threads, size_t shm) {
 
 extern "C" int ls_gemm_occupancy(int32_t which) {
   switch (which) {
-    case 1: return occ(conv_gemm_dma_kernel<128, 160, 2, 2, 1, false, 2, 64, EPI_PLAIN>, 256,
+    case 1: return occ(conv_gemm_dma_kernel<128, 160, 2, 2, 1, false, EPI_PLAIN>, 256,
                        (size_t)2 * (128 + 160) * 8 * 16);
     case 2: return occ(conv_gemm_big_kernel<256, 1, false, EPI_PLAIN>, 512, (size_t)2 * (256 + 256) * 8 * 16);
-    case 3: return occ(conv_gemm_dma_kernel<128, 128, 2, 2, 1, false, 2, 64, EPI_PLAIN>, 256,
+    case 3: return occ(conv_gemm_dma_kernel<128, 128, 2, 2, 1, false, EPI_PLAIN>, 256,
                        (size_t)2 * (128 + 128) * 8 * 16);
     default: return fail(LS_ERR_INVALID, "ls_gemm_occupancy: which 1..3");
   }
@@ -3356,30 +2727,13 @@ extern "C" int ls_conv2d(const ls_conv_desc* d, void* stream) {
   const bool vec = (a.N % 8 == 0) && (a.ldy % 8 == 0) && (!a.res || a.ldr % 8 == 0);
   // (not the 256-row kernels: compiled in, the sums cost their main loop ~12 % -- they run
   // at the 256-VGPR limit -- against a ~15 us read pass; same-box A/B, scripts/ab_lib.sh)
-  const bool cs_epi = cs && !tphase && a.split == 1 && vec && !(t.bm == 128 && t.bn == 32) && t.bm != 64 &&
-                      (t.bm < 256 || (t.bm == 260 && epi_kind(a) == EPI_PLAIN));
+  const bool cs_epi = cs && !tphase && a.split == 1 && vec && !(t.bm == 128 && t.bn == 32) && t.bm != 64 && t.bm < 256;
   if (cs_epi) a.cs_out = cs;
-#ifdef LS_DIAG_KERNELS
-  if (t.bm == 260) {  // 256 x 128, 3-stage ring (short-K linears)
-    switch (epi_kind(a)) {
-      case EPI_PLAIN: launch_dma1<256, 128, 4, 2, 1, false, 3, 64, EPI_PLAIN, true>(a, grid, s); break;
-      case EPI_GEGLU: launch_dma1<256, 128, 4, 2, 1, false, 3, 64, EPI_GEGLU, true>(a, grid, s); break;
-      default: launch_dma1<256, 128, 4, 2, 1, false, 3, 64, EPI_ANY, true>(a, grid, s);
-    }
-  } else if (t.bm == 257 && !a.aff_scale && !g_force_regstage && (d->ksize == 1 || tapu)) {  // phased 256x256
-    if (d->ksize == 1) launch_p8_1<1, false>(a, grid, s);
-    else launch_p8_1<3, true>(a, grid, s);
-  } else if (t.bm == 258 && !a.aff_scale && !g_force_regstage && (d->ksize == 1 || tapu)) {  // 4-stage BK 32
-    if (d->ksize == 1) launch_big4<1, false>(a, grid, s);
-    else launch_big4<3, true>(a, grid, s);
-  } else
-#endif
   if (t.bm == 256 && !a.aff_scale && !g_force_regstage) {
     if (t.bn == 256) launch_big<256>(a, d->ksize, tapu, grid, s);
     else launch_big<128>(a, d->ksize, tapu, grid, s);
   } else if (t.bm == 128 && t.bn == 128) launch_cfg<128, 128, 2, 2>(a, d->ksize, tapu, grid, s);
   else if (t.bm == 128 && t.bn == 160) launch_cfg<128, 160, 2, 2>(a, d->ksize, tapu, grid, s);
-
   else if (t.bm == 128 && t.bn == 64) launch_cfg<128, 64, 2, 2>(a, d->ksize, tapu, grid, s);
   else if (t.bm == 128 && t.bn == 32) launch_cfg<128, 32, 4, 1>(a, d->ksize, tapu, grid, s);
   else launch_cfg<64, 64, 2, 2>(a, d->ksize, tapu, grid, s);

@@ -52,7 +52,7 @@ struct TAttnArgs {
   u16* o;
   int ldx, ldo, F, S, blocks_per_sample;
   float eps;
-  int ablate;  // diagnostic builds only (-DLS_TATTN_ABLATE, env LS_TATTN_ABLATE): parts skipped
+  int ablate;  // diagnostic builds only (-DLS_TATTN_ABLATE; set it in ls_temporal_attention): parts skipped
 };
 
 #ifdef LS_TATTN_ABLATE
@@ -227,7 +227,7 @@ __global__ void __launch_bounds__(TCfg<C>::NT, TCfg<C>::MINB) tattn_fused_kernel
       // fragments of k-step s + 1 are read while the MFMAs of k-step s issue (double
       // buffer), so the LDS latency hides behind this wave's own matrix work
       auto frag = [&](int s, int j) {
-        return __builtin_bit_cast(bf16x8, cur[(s >> 1) * (8 * BN) + swz_bk<64>(j * 16 + l16, (s & 1) * 4 + lg)]);
+        return __builtin_bit_cast(bf16x8, cur[(s >> 1) * (8 * BN) + swz64(j * 16 + l16, (s & 1) * 4 + lg)]);
       };
       bf16x8 bw[2][FN];
 #pragma unroll
@@ -358,9 +358,6 @@ extern "C" int ls_temporal_attention(const ls_tattn_desc* d, void* stream) {
   a.ldx = d->ldx; a.ldo = d->ldo; a.F = d->F; a.S = d->S; a.blocks_per_sample = d->S / ppb;
   a.eps = d->eps > 0.f ? d->eps : 1e-5f;
   a.ablate = 0;
-#ifdef LS_TATTN_ABLATE
-  if (const char* e = ls_env("LS_TATTN_ABLATE")) a.ablate = atoi(e);
-#endif
   const int grid = d->n_samples * a.blocks_per_sample;
   hipStream_t s = (hipStream_t)stream;
   return d->C == 320 ? launch_tattn<320>(a, grid, s) : launch_tattn<640>(a, grid, s);

@@ -403,12 +403,11 @@ extern "C" int ls_groupnorm_apply(const uint16_t* x1, const uint16_t* x2, int32_
   const int ccb = std::min(CC, 256);
   const int ppb = std::max(1, 256 / ccb);
   const int threads = (ppb * ccb + 63) / 64 * 64;  // 1280 channels: 3 waves, 160 live lanes
-  static const bool v1 = ls_env("LS_GN_APPLY_V1") != nullptr;  // A/B switch: the grid-stride kernel
   constexpr int U = 4;
   const long ublocks = (n_pix + (long)U * ppb - 1) / ((long)U * ppb);
   // (C >= 1280 -- one pixel per block pass -- stays on the grid-stride kernel: 37 vs 41 us
   // at 8x8 / 32 windows; C <= 640 and the VAE 12-17 % faster, profiles/r03c_gn_apply_ab.txt)
-  if (!v1 && ppb >= 2 && (((uintptr_t)scale | (uintptr_t)shift) & 15) == 0 && (long)U * ppb <= pps &&
+  if (ppb >= 2 && (((uintptr_t)scale | (uintptr_t)shift) & 15) == 0 && (long)U * ppb <= pps &&
       ublocks < 0x7fffffffL) {
     gn_apply_u_kernel<U><<<dim3((unsigned)ublocks, cdiv(CC, ccb)), threads, 0, (hipStream_t)stream>>>(
         x1, x2, C1, C2, n_pix, pps, scale, shift, silu_on, y, ppb, ccb);

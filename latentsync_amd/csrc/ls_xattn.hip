@@ -139,7 +139,7 @@ __global__ void __launch_bounds__(512, 1) xattn_fused_kernel(XAArgs a) {
     for (int s = 0; s < 10; ++s)
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
-        const bf16x8 wf = __builtin_bit_cast(bf16x8, w[(s >> 1) * 384 + swz_bk<64>(t * 16 + l16, (s & 1) * 4 + lg)]);
+        const bf16x8 wf = __builtin_bit_cast(bf16x8, w[(s >> 1) * 384 + swz64(t * 16 + l16, (s & 1) * 4 + lg)]);
         qa[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, ar[s], qa[t], 0, 0, 0);
       }
     bf16x8 qk0, qk1;

@@ -14,10 +14,10 @@ from . import _lib
 from ._lib import check
 
 ACT_NONE, ACT_GEGLU, ACT_GELU, ACT_SILU = 0, 1, 2, 3
-_GN_EPILOGUE = _lib.ab_switch("LS_GN_EPILOGUE", "1") != "0"  # A/B switch (diagnostics): 0 = GN stats by read pass
+_GN_EPILOGUE = True  # False: GroupNorm statistics by a read pass (tests patch it)
 GN_SLOT_ROWS = 128  # LS_GN_SLOT_ROWS
-# A/B switch (diagnostics): 0 = upsample convs with phase-packed weights (Packed.phase) stay on the 9-tap form
-_UPS_PHASE = _lib.ab_switch("LS_UPS_PHASE", "1") != "0"
+# False: upsample convs with phase-packed weights (Packed.phase) stay on the 9-tap form (tests patch it)
+_UPS_PHASE = True
 
 
 def _p(t):

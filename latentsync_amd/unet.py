@@ -26,27 +26,27 @@ from dataclasses import dataclass
 
 import torch
 
-from . import _lib, ops
+from . import ops
 from .config import STAGE2_MODEL
 from .packing import geglu_interleave, pack_ff_w2, pack_phase_weight, pack_weight, pad_bias
 from .schema import unet_param_shapes
 from .weights import fill_state_dict
 
-# A/B switches (read from the environment only in diagnostics mode, _lib.ab_switch):
-# LS_FUSED_TEMPORAL=0: the motion attention as q|k|v GEMM + ls_attention
-_FUSED_TEMPORAL = _lib.ab_switch("LS_FUSED_TEMPORAL", "1") != "0"
-# LS_FUSED_FF=0: the FeedForward as GEGLU row-block GEMM + W2 GEMM
-_FUSED_FF = _lib.ab_switch("LS_FUSED_FF", "1") != "0"
-# LS_FF_CHAIN=0: the 32x32-level block tail (to_out + LN + FeedForward + proj_out) as three
+# Dispatch constants (nothing reads the environment; tests and tools patch them):
+# False: the motion attention as q|k|v GEMM + ls_attention
+_FUSED_TEMPORAL = True
+# False: the FeedForward as GEGLU row-block GEMM + W2 GEMM
+_FUSED_FF = True
+# False: the 32x32-level block tail (to_out + LN + FeedForward + proj_out) as three
 # launches (row-block GEMM, ls_feedforward, row-block GEMM) instead of one ls_ff_chain
-_FF_CHAIN = _lib.ab_switch("LS_FF_CHAIN", "1") != "0"
+_FF_CHAIN = True
 # conv_norm_out + SiLU + conv_out on the narrow halo tile, conv_out padded to 8 columns (round 6;
-# "0" in diagnostics mode: the materialised GroupNorm and the 4-column tiled GEMM)
-_NARROW_OUT = _lib.ab_switch("LS_NARROW_OUT", "1") != "0"
-# LS_FUSED_XATTN=1: the audio cross-attention branch at C = 320 as ONE ls_cross_attention_block
+# False: the materialised GroupNorm and the 4-column tiled GEMM)
+_NARROW_OUT = True
+# True: the audio cross-attention branch at C = 320 as ONE ls_cross_attention_block
 # launch instead of q GEMM + ls_attention + out GEMM.  Off by default: measured 1-2 ms per
 # 48-window step SLOWER than the three launches (profiles/r04k_step_ab.txt)
-_FUSED_XATTN = _lib.ab_switch("LS_FUSED_XATTN", "0") == "1"
+_FUSED_XATTN = False
 
 
 def _ff(h, st, ff1, ff2, ff2p):

@@ -1,5 +1,5 @@
 """Attention micro-benchmark on the UNet's shapes (graph-timed, 8 windows):
-python scripts/attn_bench.py   (LS_ATTN_V1=1 forces the 16-query kernel)."""
+python scripts/attn_bench.py"""
 import os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -65,7 +65,7 @@ def run():
             e0.record(); g.replay(); e1.record(); torch.cuda.synchronize()
             ts.append(e0.elapsed_time(e1) / 5)
         t = statistics.median(ts)
-        print(f"{'fp8' if FP8 and kind == 'self' else os.environ.get('LS_ATTN_V1', 'v2'):3s} {name:18s} {t*1e3:9.1f} us {flops/t/1e9:8.1f} TF/s")
+        print(f"{'fp8' if FP8 and kind == 'self' else 'v2':3s} {name:18s} {t*1e3:9.1f} us {flops/t/1e9:8.1f} TF/s")
         if kind != "temporal" and not os.environ.get("NO_SDPA"):  # torch SDPA (vendor flash attention) on the same problem, (B, H, N, d)
             qt = torch.randn(n, heads, N, d, device="cuda", dtype=torch.bfloat16)
             kt = torch.randn(n, heads, Nk, d, device="cuda", dtype=torch.bfloat16)

@@ -86,24 +86,19 @@ def run(tag, reps=20, scale=1):
 
 
 if __name__ == "__main__":
-    # modes: dma reg nomfma nodma bk32 t1..t6 (forced tile id); suffix @4 = 4x the frames
+    # modes: dma reg nomfma nodma t1..t6 (forced tile id); suffix @4 = 4x the frames
     for arg in sys.argv[1:] or ["dma"]:
         mode, _, sc = arg.partition("@")
-        # mode parts joined by '+': reg, bk32, tN (forced tile id), abN (ablation bits), nomfma, nodma
+        # mode parts joined by '+': reg, tN (forced tile id), abN (ablation bits), norb, nohalo, bn128, nomfma, nodma
         parts = mode.split("+")
         ab = {"nomfma": 1, "nodma": 2}.get(mode, 0)
         ab |= sum(int(p[2:]) for p in parts if p.startswith("ab"))
         tile = [int(p[1:]) for p in parts if p.startswith("t") and p[1:].isdigit()]
         lib.ls_set_tuning(1, 1 if "reg" in parts else 0)
         lib.ls_set_tuning(4, ab)
-        lib.ls_set_tuning(5, 32 if "bk32" in parts else 64)
         lib.ls_set_tuning(2, tile[0] if tile else 0)
         lib.ls_set_tuning(6, 0 if "norb" in parts else 1)
         lib.ls_set_tuning(8, 0 if "nohalo" in parts else 1)
-        lib.ls_set_tuning(10, 1 if "t256" in parts else 0)
-        lib.ls_set_tuning(11, 1 if "rs" in parts else 0)
-        lib.ls_set_tuning(12, 0 if "nohrp" in parts else 1)
         lib.ls_set_tuning(13, 1 if "bn128" in parts else 0)
-        lib.ls_set_tuning(14, 1 if "areg" in parts else 0)
         TORCH_REF = "torch" in parts
         run(arg, scale=int(sc or 1))

@@ -1,5 +1,5 @@
 """GroupNorm stats / apply micro-benchmark on the UNet's shapes (WINDOWS windows, default 32) and two
-VAE shapes (64 images).  LS_GN_APPLY_V1=1: the grid-stride apply kernel."""
+VAE shapes (64 images)."""
 import os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -25,5 +25,5 @@ for (n, H, C) in [(16 * W, 32, 320), (16 * W, 16, 640), (16 * W, 8, 1280), (16 *
     sc, sh = ops.group_norm(x, 32, 1e-5, g, b, B)
     ta = timeit(lambda: ops.group_norm_apply(x, sc, sh, B, True))
     mb = x.numel() * 2 / 1e6
-    print(f"v1={os.environ.get('LS_GN_APPLY_V1', '0')} GN {n}x{H}x{H}x{C}: stats {t:7.1f} us ({mb / t:5.2f} TB/s)  "
+    print(f"GN {n}x{H}x{H}x{C}: stats {t:7.1f} us ({mb / t:5.2f} TB/s)  "
           f"apply {ta:7.1f} us ({2 * mb / ta:5.2f} TB/s)")

@@ -89,19 +89,14 @@ def chain_setup(M):
     return c, pk, g, d
 
 
-@pytest.mark.parametrize("fmr", [1, 2])
+@pytest.mark.parametrize("fmr", [1])  # 16 rows per wave, the only form
 @pytest.mark.parametrize("M", P.FF_CHAIN_M)
 def test_ff_chain(gpu, M, fmr):
     lib = _lib.load()
     c, pk, g, d = chain_setup(M)
     ins = [(t, P.snapshot(t)) for t in (g["o"].buf, g["h1"].buf, g["xb"].buf, pk.wo, pk.w1, pk.w2, pk.wp, pk.b1)]
-    if lib.ls_set_tuning(17, fmr) != 0:  # rows per wave: 16 (default) / 32 (diagnostics build)
-        pytest.skip("32 rows per wave: diagnostics build only")
-    try:
-        _lib.check(lib.ls_ff_chain(ctypes.byref(d), _stream()), "ls_ff_chain")
-        torch.cuda.synchronize()
-    finally:
-        lib.ls_set_tuning(17, 1)
+    _lib.check(lib.ls_ff_chain(ctypes.byref(d), _stream()), "ls_ff_chain")
+    torch.cuda.synchronize()
     name = f"ff_chain M {M} fmr {fmr}"
     P.assert_guard_intact(g["z"], f"{name} z")
     P.assert_guard_intact(g["cs"], f"{name} cs_out")

@@ -56,8 +56,8 @@ class tuning:
     def __enter__(self):
         try:
             for k, v in self.keys.items():
-                if self.lib.ls_set_tuning(k, v) != 0:
-                    pytest.skip(f"ls_set_tuning({k}, {v}) refused: {self.lib.ls_last_error().decode()}")
+                assert self.lib.ls_set_tuning(k, v) == 0, \
+                    f"ls_set_tuning({k}, {v}) refused: {self.lib.ls_last_error().decode()}"
         except BaseException:
             self.__exit__()
             raise
