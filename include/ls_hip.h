@@ -136,7 +136,8 @@ typedef struct {
 #define LS_GN_SLOT_ROWS 128
 
 int ls_conv2d(const ls_conv_desc* d, void* stream);
-/* Which kernel family ls_conv2d would run for d: 0 = tiled DMA GEMM, 1 = row-block
+/* Which kernel family ls_conv2d will launch for d (the family of its plan, see ls_conv_plan:
+ * the same decision, taken once, not a separate walk): 0 = tiled DMA GEMM, 1 = row-block
  * GEMM (K = 320 / 640 linears; also takes the GroupNorm affine prologue on its
  * register-resident A rows), 2 = register-staged tiled GEMM (affine prologue
  * elsewhere -- callers materialise the affine with ls_groupnorm_apply instead),
@@ -149,6 +150,39 @@ int ls_conv2d(const ls_conv_desc* d, void* stream);
  * Host-only, no launch. */
 int ls_conv_path(const ls_conv_desc* d);
 size_t ls_conv_workspace_bytes(const ls_conv_desc* d);
+
+/* The plan of an ls_conv2d call: the one kernel instance it launches, with its geometry, and
+ * the passes that follow it.  ls_conv2d makes this plan and runs it; ls_conv_path is its
+ * `family`, ls_conv_workspace_bytes its `workspace_bytes`.  The order of the decision:
+ *   1. upsample = 2: the halo-tile kernel's phase form (4), else the tiled one (5), else an error;
+ *   2. the halo-tile 3x3 conv (3);
+ *   3. the row-block GEMM (1) with row_stats_out and gn_colsum_out in its epilogue;
+ *   4. the row-block GEMM with row_stats_out, gn_colsum_out by a read pass over y;
+ *   5. with row_stats_out and no such instance: the row-block GEMM without the statistics
+ *      (gn_colsum_out in the epilogue, else by the read pass), ls_row_stats over y at the end;
+ *   6. the tiled kernels (0; 2 with an affine prologue or tuning key 1): gn_colsum_out in the
+ *      epilogue where the tile has it, else by the read pass; ls_row_stats over y at the end.
+ * A split-K the workspace of d cannot hold is reduced to what fits before 1. (a NULL workspace
+ * is never split automatically).  Fields that do not apply to the family are -1. */
+typedef struct {
+  int32_t family;                  /* ls_conv_path code                                      */
+  int32_t bm, bn, ks, tapu;        /* tiled kernels: tile (bm 256: the 8-wave kernels), gather */
+  int32_t buf, epi;                /* LDS-DMA tiled kernels: buffer-descriptor DMA; epilogue
+                                      0 plain, 1 GEGLU, 2 general, 3 plain phase form         */
+  int32_t split;                   /* split-K slabs (1 = none)                               */
+  int32_t rb_kt, rb_fm, rb_flags;  /* row-block GEMM: K / 32, 16-row fragments per wave, flags 1 LN
+                                      fold, 2 residual, 4 rowvec, 8 GEGLU, 16 row statistics,
+                                      32 GroupNorm column sums, 64 affine prologue           */
+  int32_t halo_bn, halo_th, halo_gn, halo_cs, halo_ph; /* halo-tile conv: columns, patch rows,
+                                      input affine, column sums, phase form                  */
+  int32_t grid, threads, lds_bytes;  /* the launch: blocks, threads per block, dynamic LDS   */
+  int32_t reduce;                  /* trailing passes, in this order: the split-K reduce,      */
+  int32_t colsum_rows;             /* the gn_colsum_out read pass over this many rows of y (0: none), */
+  int32_t row_stats;               /* ls_row_stats over y                                    */
+  int64_t workspace_bytes;         /* what the plan's split-K asks for, before it is fitted  */
+} ls_conv_plan_info;
+/* Host-only, no launch, no GPU needed. */
+int ls_conv_plan(const ls_conv_desc* d, ls_conv_plan_info* out);
 
 /*
  * GroupNorm statistics -> per-(sample, channel) affine for the consumer's

@@ -39,6 +39,14 @@ class ConvDesc(C.Structure):
     ]
 
 
+class ConvPlanInfo(C.Structure):
+    """ls_conv_plan_info: what ls_conv2d launches for a descriptor (-1: not of this family)."""
+    _fields_ = [(f, C.c_int32) for f in (
+        "family", "bm", "bn", "ks", "tapu", "buf", "epi", "split", "rb_kt", "rb_fm", "rb_flags",
+        "halo_bn", "halo_th", "halo_gn", "halo_cs", "halo_ph", "grid", "threads", "lds_bytes",
+        "reduce", "colsum_rows", "row_stats")] + [("workspace_bytes", C.c_int64)]
+
+
 class AttnDesc(C.Structure):
     _fields_ = [("q", c_vp), ("k", c_vp), ("v", c_vp), ("o", c_vp)] + [
         (f"{t}_{s}", C.c_int64) for t in "qkvo" for s in ("sb1", "sb2", "si", "sh")
@@ -80,6 +88,7 @@ _SIGS = {
     "ls_conv2d": (C.c_int, [C.POINTER(ConvDesc), c_vp]),
     "ls_conv_workspace_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
     "ls_conv_path": (C.c_int, [C.POINTER(ConvDesc)]),
+    "ls_conv_plan": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvPlanInfo)]),
     "ls_groupnorm": (C.c_int, [c_vp, c_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float,
                                c_vp, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
     "ls_groupnorm_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),

@@ -2147,6 +2147,29 @@ static int g_force_tile = 0, g_force_split = 0;  // tuning keys 2, 3
 // 4 no output store, 8 the general epilogue arithmetic even where the short path applies
 static int g_ablate = 0;
 
+// The plan of one ls_conv2d call.  plan_conv takes every decision once -- the kernel family,
+// the instance within it, the launch geometry and the passes that follow -- and ls_conv2d,
+// ls_conv_path, ls_conv_plan and ls_conv_workspace_bytes all read that one answer.
+struct ConvPlan {
+  ConvArgs a;           // exactly as the kernel receives it
+  ls_conv_plan_info i;  // family, instance, geometry, trailing passes (ls_hip.h)
+  float* cs_pass;       // launch_colsum_pass over the stored y (i.colsum_rows rows) into this, or null
+  float* row_stats;     // ls_row_stats of the stored y into this, or null
+};
+
+template <int V>
+using IC = std::integral_constant<int, V>;
+
+// launches the plan's kernel instance with the plan's geometry
+template <void (*KERN)(ConvArgs)>
+static void launch_plan(const ConvPlan& p, hipStream_t s) {
+  if (p.i.lds_bytes) LS_SET_MAX_DYN_SHM(KERN, p.i.lds_bytes);
+  KERN<<<p.i.grid, p.i.threads, p.i.lds_bytes, s>>>(p.a);
+}
+
+// 16-B rows in the epilogue (else the tiled kernels store element by element)
+static bool vec_ok(const ConvArgs& a) { return a.N % 8 == 0 && a.ldy % 8 == 0 && (!a.res || a.ldr % 8 == 0); }
+
 struct TileCfg { int bm, bn, split; };
 
 // Tile + split-K choice by a small cost model.  A CU runs up to R blocks of a tile
@@ -2191,10 +2214,20 @@ static TileCfg pick_tile(long M, int N, int ktiles, bool allow_split, bool big_o
   return best;
 }
 
-// ---- row-block GEMM dispatch (gemm_rowblock_kernel)
+// split-K slabs of whole K-tiles: at most `split` of them, none empty
+static void set_split(ConvArgs& a, int split) {
+  a.kt_per_split = cdiv(a.ktiles, std::max(1, std::min(split, a.ktiles)));
+  a.split = cdiv(a.ktiles, a.kt_per_split);
+}
+
+// ---- row-block GEMM (gemm_rowblock_kernel)
 static bool g_rowblock = true;     // tuning key 6
 static bool g_rowblock640 = true;  // tuning key 7
 static bool g_rb640_res = false;   // tuning key 20: K = 640 residual GEMMs too
+// K = 640 with two 16-row fragments per wave (256-row blocks, half the W-fragment LDS reads
+// per MFMA, 160 A registers): default since r04x (step 215.3 -> 212.2 ms at 48 windows, three
+// same-box alternations); tuning key 15 = 0: one fragment per wave
+static bool g_rb640_fm2 = true;
 
 static bool rowblock_ok(const ls_conv_desc* d, const ConvArgs& a) {
   if (!g_rowblock || g_force_tile || g_force_regstage || d->ksize != 1 || a.C2) return false;
@@ -2213,113 +2246,79 @@ static bool rowblock_ok(const ls_conv_desc* d, const ConvArgs& a) {
   return (((uintptr_t)a.x1 | (uintptr_t)a.bias | (uintptr_t)a.ln_cs | (uintptr_t)a.rowvec) & 15) == 0;
 }
 
+// the compiled FLAGS combinations, each at <KT 10, FM 2>, <20, 1> and, without RB_FM1, <20, 2>
+using RowblockInstances =
+    std::integer_sequence<int, 0, RB_LN, RB_LN | RB_RV, RB_RES, RB_LN | RB_RES, RB_LN | RB_GEGLU, RB_GEGLU, RB_STATS,
+                          RB_RES | RB_STATS, RB_RES | RB_GNCS, RB_AFF, RB_AFF | RB_STATS>;
+// one fragment per wave only: the statistics epilogues spill at FM 2, and with the GroupNorm
+// affine a block looks its sample up once (rowblock_ok only guarantees pix_per_sample % 128
+// == 0 at K = 640)
+constexpr int RB_FM1 = RB_STATS | RB_GNCS | RB_AFF;
+
 // FN = 2 (32-column chunks): the FN = 4 variant needs > 256 VGPRs and spills, and a
 // spill's scratch traffic would break the kernel's counted vmcnt waits.
-template <int KT, int FM, int FLAGS>
-static void launch_rowblock2(const ConvArgs& a, int grid, hipStream_t s) {
-  constexpr int FN = 2;
-  constexpr int BM = 8 * 16 * FM;
-  const size_t shm = (size_t)3 * (16 * FN * (KT / 2) * 8 + 48 + ((FLAGS & RB_RES) ? BM * 16 * FN / 8 : 0)) * 16 +
-                     ((FLAGS & RB_GNCS) ? 4096 : 0);
-  LS_SET_MAX_DYN_SHM((gemm_rowblock_kernel<KT, FM, FN, FLAGS>), (int)shm);
-  gemm_rowblock_kernel<KT, FM, FN, FLAGS><<<grid, 512, shm, s>>>(a);
+constexpr size_t rowblock_lds(int kt, int fm, int flags) {
+  return (size_t)3 * (16 * 2 * (kt / 2) * 8 + 48 + ((flags & RB_RES) ? 128 * fm * 16 * 2 / 8 : 0)) * 16 +
+         ((flags & RB_GNCS) ? 4096 : 0);
 }
 
-// K = 640 with two 16-row fragments per wave (256-row blocks, half the W-fragment LDS reads
-// per MFMA, 160 A registers): default since r04x (step 215.3 -> 212.2 ms at 48 windows, three
-// same-box alternations); tuning key 15 = 0: one fragment per wave
-static bool g_rb640_fm2 = true;
-
-static bool rb640_fm2(int flags);
-
-template <int FLAGS>
-static void launch_rowblock1(const ConvArgs& a, int grid, hipStream_t s) {
-  if (a.K == 320) {
-    launch_rowblock2<10, 2, FLAGS>(a, grid, s);
-    return;
-  }
-  if constexpr (!(FLAGS & (RB_STATS | RB_GNCS | RB_AFF))) {  // (the statistics epilogues spill at FM 2)
-    if (rb640_fm2(FLAGS)) {
-      launch_rowblock2<20, 2, FLAGS>(a, grid, s);
-      return;
-    }
-  }
-  launch_rowblock2<20, 1, FLAGS>(a, grid, s);
+template <int... F>
+static bool rowblock_compiled(int flags, std::integer_sequence<int, F...>) {
+  return ((flags == F) || ...);
 }
 
-// returns false when no instance matches (the caller then uses the tiled kernels)
-// compiled row-block instances (FLAGS combinations)
-static const int kRowblockInstances[] = {0, RB_LN, RB_LN | RB_RV, RB_RES, RB_LN | RB_RES, RB_LN | RB_GEGLU, RB_GEGLU,
-                                         RB_STATS, RB_RES | RB_STATS, RB_RES | RB_GNCS, RB_AFF, RB_AFF | RB_STATS};
-
-// the row-block instance flags for this call, or -1; the row-block grid goes to
-// *ntm / *ntn only (the caller's tiled grid in a.ntm / a.ntn stays valid for a fallback)
-// (not with the GroupNorm affine: a block looks its sample up once, and rowblock_ok only
-// guarantees pix_per_sample % 128 == 0 at K = 640)
-static bool rb640_fm2(int flags) { return g_rb640_fm2 && !(flags & (RB_STATS | RB_GNCS | RB_AFF)); }
-
-static int rowblock_flags(const ConvArgs& a, int* ntm_out, int* ntn_out) {
+// Plans the row-block instance for a.stats_out / a.cs_out as they stand; false when there is
+// none (fused statistics and column sums need whole rows in a block).
+static bool plan_rowblock(ConvPlan& p) {
+  ConvArgs& a = p.a;
   const int flags = (a.ln_mr ? RB_LN : 0) | (a.res ? RB_RES : 0) | (a.rowvec ? RB_RV : 0) |
                     (a.act == LS_ACT_GEGLU ? RB_GEGLU : 0) | (a.stats_out ? RB_STATS : 0) | (a.cs_out ? RB_GNCS : 0) |
                     (a.aff_scale ? RB_AFF : 0);
-  const int bm = a.K == 320 || rb640_fm2(flags) ? 256 : 128;
-  if (a.M % bm) return -1;
+  const int fm = a.K == 320 || (g_rb640_fm2 && !(flags & RB_FM1)) ? 2 : 1, bm = 128 * fm;
+  if (a.M % bm || !rowblock_compiled(flags, RowblockInstances{})) return false;
   const int ntm = a.M / bm, nch = a.N / 32;
   const int ntn = std::max(1, std::min(nch, (256 + ntm - 1) / ntm));
-  if (a.stats_out && ntn != 1) return -1;  // fused statistics need whole rows per block
-  if (a.cs_out && (bm % CS_ROWS || ntn != 1)) return -1;
-  for (int f : kRowblockInstances)
-    if (f == flags) {
-      *ntm_out = ntm;
-      *ntn_out = ntn;
-      return flags;
-    }
-  return -1;
-}
-
-// returns false when no instance matches (the caller then uses the tiled kernels with
-// its own, untouched a.ntm / a.ntn)
-static bool launch_rowblock(const ConvArgs& a0, hipStream_t s) {
-  int ntm = 0, ntn = 0;
-  const int flags = rowblock_flags(a0, &ntm, &ntn);
-  if (flags < 0) return false;
-  ConvArgs a = a0;
+  if ((a.stats_out || a.cs_out) && ntn != 1) return false;
   a.ntm = ntm;
   a.ntn = ntn;
-  const int grid = ntm * ntn;
-  switch (flags) {
-    case 0: launch_rowblock1<0>(a, grid, s); return true;
-    case RB_LN: launch_rowblock1<RB_LN>(a, grid, s); return true;
-    case RB_LN | RB_RV: launch_rowblock1<RB_LN | RB_RV>(a, grid, s); return true;
-    case RB_RES: launch_rowblock1<RB_RES>(a, grid, s); return true;
-    case RB_LN | RB_RES: launch_rowblock1<RB_LN | RB_RES>(a, grid, s); return true;
-    case RB_LN | RB_GEGLU: launch_rowblock1<RB_LN | RB_GEGLU>(a, grid, s); return true;
-    case RB_GEGLU: launch_rowblock1<RB_GEGLU>(a, grid, s); return true;
-    case RB_STATS: launch_rowblock1<RB_STATS>(a, grid, s); return true;
-    case RB_RES | RB_STATS: launch_rowblock1<RB_RES | RB_STATS>(a, grid, s); return true;
-    case RB_RES | RB_GNCS: launch_rowblock1<RB_RES | RB_GNCS>(a, grid, s); return true;
-    case RB_AFF: launch_rowblock1<RB_AFF>(a, grid, s); return true;
-    case RB_AFF | RB_STATS: launch_rowblock1<RB_AFF | RB_STATS>(a, grid, s); return true;
-    default: return false;
+  p.i.family = 1;
+  p.i.rb_kt = a.K / 32;
+  p.i.rb_fm = fm;
+  p.i.rb_flags = flags;
+  p.i.grid = ntm * ntn;
+  p.i.threads = 512;
+  p.i.lds_bytes = (int)rowblock_lds(p.i.rb_kt, fm, flags);
+  return true;
+}
+
+template <int FLAGS>
+static void launch_rowblock1(const ConvPlan& p, hipStream_t s) {
+  if (p.i.rb_kt == 10) return launch_plan<gemm_rowblock_kernel<10, 2, 2, FLAGS>>(p, s);
+  if constexpr (!(FLAGS & RB_FM1)) {
+    if (p.i.rb_fm == 2) return launch_plan<gemm_rowblock_kernel<20, 2, 2, FLAGS>>(p, s);
   }
+  launch_plan<gemm_rowblock_kernel<20, 1, 2, FLAGS>>(p, s);
+}
+
+template <int... F>
+static void launch_rowblock(const ConvPlan& p, hipStream_t s, std::integer_sequence<int, F...>) {
+  ((p.i.rb_flags == F ? launch_rowblock1<F>(p, s) : void()), ...);
+}
+
+// ---- tiled kernels (conv_gemm_kernel, conv_gemm_dma_kernel, conv_gemm_big_kernel)
+// dynamic LDS of the DMA kernels: two stages of 64-deep K-tiles; staging for the epilogue
+// (the bm / wm rows of a wave row; 128 in the 8-wave 256-row kernels) must fit too
+constexpr size_t tiled_lds(int bm, int bn, int wm) {
+  return std::max<size_t>((size_t)2 * (bm + bn) * 8 * 16, (size_t)(bm / wm) * (bn + 4) * 4);
 }
 
 // epilogue variant of a launch (see store_tile)
 static int epi_kind(const ConvArgs& a) {
   if (a.phase) return EPI_PLAINP;  // (tiled_phase_ok: the plain epilogue's conditions hold)
-  const bool vec = (a.N % 8 == 0) && (a.ldy % 8 == 0) && (!a.res || a.ldr % 8 == 0);
-  if (a.split != 1 || !vec || a.y_f32) return EPI_ANY;
+  if (a.split != 1 || !vec_ok(a) || a.y_f32) return EPI_ANY;
   if (a.act == LS_ACT_NONE) return EPI_PLAIN;
   if (a.act == LS_ACT_GEGLU) return EPI_GEGLU;
   return EPI_ANY;
-}
-
-template <int BM, int BN, int WM, int WN, int KS, bool TAPU, int EPI, bool BUF = false>
-static void launch_dma1(const ConvArgs& a, int grid, hipStream_t s) {
-  // two stages of 64-deep K-tiles; staging for the epilogue must fit too
-  const size_t shm = std::max<size_t>((size_t)2 * (BM + BN) * 8 * 16, (size_t)(BM / WM) * (BN + 4) * 4);
-  LS_SET_MAX_DYN_SHM((conv_gemm_dma_kernel<BM, BN, WM, WN, KS, TAPU, EPI, BUF>), (int)shm);
-  conv_gemm_dma_kernel<BM, BN, WM, WN, KS, TAPU, EPI, BUF><<<grid, WM * WN * 64, shm, s>>>(a);
 }
 
 // operand DMA through buffer descriptors: 1x1 with K == Cin, Cin % 64 == 0; tap-major 3x3,
@@ -2332,136 +2331,89 @@ static bool buf_dma_ok(const ConvArgs& a, int ks) {
   return a.Cin % 64 == 0 && a.C1 % 64 == 0 && (a.stride == 1 || a.stride == 2) && (a.pad == 0 || a.pad == 1);
 }
 
-template <int BM, int BN, int WM, int WN, int KS, bool TAPU>
-static void launch_dma(const ConvArgs& a, int grid, hipStream_t s) {
-  if constexpr (KS == 1 || TAPU) {
-    if constexpr (KS == 3 && TAPU) {  // the tiled phase form (tiled_phase_ok: buffer-descriptor DMA)
-      if (a.phase) { launch_dma1<BM, BN, WM, WN, KS, TAPU, EPI_PLAINP, true>(a, grid, s); return; }
-    }
-    if (buf_dma_ok(a, KS)) {
-      switch (epi_kind(a)) {
-        case EPI_PLAIN: launch_dma1<BM, BN, WM, WN, KS, TAPU, EPI_PLAIN, true>(a, grid, s); return;
-        case EPI_GEGLU: launch_dma1<BM, BN, WM, WN, KS, TAPU, EPI_GEGLU, true>(a, grid, s); return;
-        default: launch_dma1<BM, BN, WM, WN, KS, TAPU, EPI_ANY, true>(a, grid, s); return;
-      }
-    }
-  }
-  switch (epi_kind(a)) {
-    case EPI_PLAIN: launch_dma1<BM, BN, WM, WN, KS, TAPU, EPI_PLAIN>(a, grid, s); break;
-    case EPI_GEGLU: launch_dma1<BM, BN, WM, WN, KS, TAPU, EPI_GEGLU>(a, grid, s); break;
-    default: launch_dma1<BM, BN, WM, WN, KS, TAPU, EPI_ANY>(a, grid, s);
+template <class B, class F>
+static void with_epi(int epi, B buf, F f) {
+  switch (epi) {
+    case EPI_PLAIN: return f(IC<EPI_PLAIN>{}, buf);
+    case EPI_GEGLU: return f(IC<EPI_GEGLU>{}, buf);
+    default: return f(IC<EPI_ANY>{}, buf);
   }
 }
 
-template <int BN, int KS, bool TAPU, int EPI, bool BUF = false>
-static void launch_big2(const ConvArgs& a, int grid, hipStream_t s) {
-  const size_t shm = std::max<size_t>((size_t)2 * (256 + BN) * 8 * 16, (size_t)128 * (BN + 4) * 4);
-  LS_SET_MAX_DYN_SHM((conv_gemm_big_kernel<BN, KS, TAPU, EPI, BUF>), (int)shm);
-  conv_gemm_big_kernel<BN, KS, TAPU, EPI, BUF><<<grid, 512, shm, s>>>(a);
-}
-
-template <int BN, int KS, bool TAPU>
-static void launch_big1(const ConvArgs& a, int grid, hipStream_t s) {
+// f(EPI, BUF) for the plan's epilogue and DMA form, over the instances compiled for a (KS,
+// TAPU) gather: buffer-descriptor DMA only for 1x1 and channel-chunk-major 3x3, EPI_PLAINP
+// (the tiled phase form) only for the latter and always with it
+template <int KS, bool TAPU, class F>
+static void with_epi_buf(const ls_conv_plan_info& i, F f) {
   if constexpr (KS == 3 && TAPU) {
-    if (a.phase) { launch_big2<BN, KS, TAPU, EPI_PLAINP, true>(a, grid, s); return; }
+    if (i.epi == EPI_PLAINP) return f(IC<EPI_PLAINP>{}, std::true_type{});
   }
   if constexpr (KS == 1 || TAPU) {
-    if (buf_dma_ok(a, KS)) {
-      switch (epi_kind(a)) {
-        case EPI_PLAIN: launch_big2<BN, KS, TAPU, EPI_PLAIN, true>(a, grid, s); return;
-        case EPI_GEGLU: launch_big2<BN, KS, TAPU, EPI_GEGLU, true>(a, grid, s); return;
-        default: launch_big2<BN, KS, TAPU, EPI_ANY, true>(a, grid, s); return;
-      }
-    }
+    if (i.buf) return with_epi(i.epi, std::true_type{}, f);
   }
-  switch (epi_kind(a)) {
-    case EPI_PLAIN: launch_big2<BN, KS, TAPU, EPI_PLAIN>(a, grid, s); break;
-    case EPI_GEGLU: launch_big2<BN, KS, TAPU, EPI_GEGLU>(a, grid, s); break;
-    default: launch_big2<BN, KS, TAPU, EPI_ANY>(a, grid, s);
-  }
+  with_epi(i.epi, std::false_type{}, f);
 }
 
-
-template <int BN>
-static void launch_big(const ConvArgs& a, int ks, bool tapu, int grid, hipStream_t s) {
-  if (ks == 1) launch_big1<BN, 1, false>(a, grid, s);
-  else if (tapu) launch_big1<BN, 3, true>(a, grid, s);
-  else launch_big1<BN, 3, false>(a, grid, s);
+template <int BM, int BN, int WM, int WN, int KS, bool TAPU>
+static void launch_tiled2(const ConvPlan& p, hipStream_t s) {
+  if constexpr (BM != 256) {  // (the 256-row kernels have no register-staged form)
+    if (p.i.family == 2) return launch_plan<conv_gemm_kernel<BM, BN, WM, WN, KS, TAPU>>(p, s);
+  }
+  with_epi_buf<KS, TAPU>(p.i, [&](auto epi, auto buf) {
+    constexpr int EPI = decltype(epi)::value;
+    constexpr bool BUF = decltype(buf)::value;
+    if constexpr (BM == 256) launch_plan<conv_gemm_big_kernel<BN, KS, TAPU, EPI, BUF>>(p, s);
+    else launch_plan<conv_gemm_dma_kernel<BM, BN, WM, WN, KS, TAPU, EPI, BUF>>(p, s);
+  });
 }
 
 template <int BM, int BN, int WM, int WN>
-static void launch_cfg(const ConvArgs& a, int ks, bool tapu, int grid, hipStream_t s) {
-  if (a.aff_scale || g_force_regstage) {  // prologue needs the register path
-    if (ks == 1) conv_gemm_kernel<BM, BN, WM, WN, 1, false><<<grid, 256, 0, s>>>(a);
-    else if (tapu) conv_gemm_kernel<BM, BN, WM, WN, 3, true><<<grid, 256, 0, s>>>(a);
-    else conv_gemm_kernel<BM, BN, WM, WN, 3, false><<<grid, 256, 0, s>>>(a);
-  } else {
-    if (ks == 1) launch_dma<BM, BN, WM, WN, 1, false>(a, grid, s);
-    else if (tapu) launch_dma<BM, BN, WM, WN, 3, true>(a, grid, s);
-    else launch_dma<BM, BN, WM, WN, 3, false>(a, grid, s);
-  }
+static void launch_tiled1(const ConvPlan& p, hipStream_t s) {
+  if (p.i.ks == 1) launch_tiled2<BM, BN, WM, WN, 1, false>(p, s);
+  else if (p.i.tapu) launch_tiled2<BM, BN, WM, WN, 3, true>(p, s);
+  else launch_tiled2<BM, BN, WM, WN, 3, false>(p, s);
 }
 
-// ---- halo-tile 3x3 conv dispatch (conv3x3_halo_kernel)
+static void launch_tiled(const ConvPlan& p, hipStream_t s) {
+  const int bm = p.i.bm, bn = p.i.bn;
+  if (bm == 256 && bn == 256) launch_tiled1<256, 256, 2, 4>(p, s);
+  else if (bm == 256) launch_tiled1<256, 128, 2, 4>(p, s);
+  else if (bm == 128 && bn == 128) launch_tiled1<128, 128, 2, 2>(p, s);
+  else if (bm == 128 && bn == 160) launch_tiled1<128, 160, 2, 2>(p, s);
+  else if (bm == 128 && bn == 64) launch_tiled1<128, 64, 2, 2>(p, s);
+  else if (bm == 128 && bn == 32) launch_tiled1<128, 32, 4, 1>(p, s);
+  else launch_tiled1<64, 64, 2, 2>(p, s);
+}
+
+// The phase form of an upsample conv (upsample == 2) on the tiled kernels, for what the halo
+// kernel does not take (N > 640, images its patches do not divide): per output parity a plain
+// pad-1 conv in input space over 4 of the 9 tap positions (BufDma's border masks and tap_of
+// as for any 3x3), the parity a grid slice, rows mapped to the strided output pixels in the
+// plain epilogue (EPI_PLAINP); GroupNorm column sums by the read pass over the stored output.
+static bool tiled_phase_ok(const ConvArgs& a) {
+  return a.upsample == 2 && vec_ok(a) && !a.y_f32 && a.act == LS_ACT_NONE && !a.rowvec && !a.C2 && !g_force_regstage &&
+         buf_dma_ok(a, 3);
+}
+
+static void to_tiled_phase(ConvArgs& a, int bm) {
+  a.phase = 1;  // (the kernel sets 1 + ph)
+  a.upsample = 0;
+  a.Ho = a.H;
+  a.Wo = a.W;
+  a.M = a.n_img * a.H * a.W;
+  a.ntm = cdiv(a.M, bm);
+  a.gm = std::max(1, std::min(a.gm, a.ntm));
+}
+
+// ---- halo-tile 3x3 conv (conv3x3_halo_kernel)
 static bool g_halo = true;  // tuning key 8
 // the nearest-x2 upsample convs on the halo kernel too (tuning key 18; off: the tiled gather)
 static bool g_halo_ups = true;
 // tuning key 13: 128-channel tiles where both divide N (3-slot weight ring instead of 2 at
 // BN 160)
 static bool g_halo_bn128 = false;
-
 // the narrow 16-column tile for N <= 16 (tuning key 19; off: the tiled GEMM's 128 x 32 tile)
 static bool g_halo_narrow = true;
-
-// patch width of the halo conv for this call (0: not taken)
-static int halo_tw(const ls_conv_desc* d, const ConvArgs& a) {
-  if (!g_halo || g_force_tile || g_force_regstage || d->ksize != 3 || a.stride != 1 || a.pad != 1 ||
-      !a.ccm || a.Cin % 64 || a.C1 % 64 || a.K != (a.upsample == 2 ? 4 : 9) * a.Cin || a.y_f32 || a.act != LS_ACT_NONE ||
-      a.ln_mr || a.stats_out || a.ldy % 8 || (a.res && a.ldr % 8))
-    return 0;
-  // nearest x2 upsample (Upsample3D, resnet.py:53-71; round 6): no input affine (the UNet's
-  // upsampler conv has none); the halo image is built in output space from the input pixels
-  if (a.upsample ? (!g_halo_ups || a.aff_scale || a.Ho != 2 * a.H || a.Wo != 2 * a.W) : (a.Ho != a.H || a.Wo != a.W))
-    return 0;
-  // N <= 640: with more output channels the patch is re-loaded and re-transformed per N tile
-  // and the tiled 256x256 kernel wins (VAE 512 channels at 32^2: 3667 vs 3409 us; 128 at
-  // 256^2: 18660 vs 23610 us incl. the materialised GroupNorm; profiles/r04f_ab_t256_halo.txt)
-  // (N = 8 / 16: the narrow tile -- conv_out of the VAE decoder / encoder, N padded to 8)
-  const bool narrow = a.N % 8 == 0 && a.N <= 16 && a.H % 8 == 0 && g_halo_narrow;
-  if (((a.N % 160 && a.N % 128) || a.N > 640) && !narrow) return 0;
-  if (a.aff_scale && (!a.silu_in || a.pix_per_sample % (a.H * a.W) || ((uintptr_t)a.aff_scale | (uintptr_t)a.aff_shift) & 15))
-    return 0;  // (the kernel's input transform is the GroupNorm affine + SiLU of a ResnetBlock)
-  if (((uintptr_t)a.x1 | (uintptr_t)a.x2 | (uintptr_t)a.w) & 15 || a.ld1 % 8 || (a.C2 && a.ld2 % 8)) return 0;
-  // 16 x 16 patches everywhere: the smallest halo overhead ((16 + 2)^2 / 256 = 1.27 input
-  // pixels per output pixel; 32 x 8: 1.33, 64 x 4: 1.55) and no register spills
-  // (the phase form of an upsample conv, upsample == 2, patches the INPUT image)
-  const int tw = (a.upsample == 2 ? a.W % 16 == 0 && a.H % 16 == 0 : a.Wo % 16 == 0 && a.Ho % 16 == 0) ? 16 : 0;
-  if (!tw) return 0;
-  if (a.upsample == 2 && (a.N <= 16 || a.C2)) return 0;  // (no narrow tile, one source)
-  if ((long)a.H * a.W * a.ld1 * 2 >= (1L << 31) || (a.C2 && (long)a.H * a.W * a.ld2 * 2 >= (1L << 31)))
-    return 0;  // per-image buffer descriptors
-  return tw;
-}
-
-template <int TW, int BN, bool GN, bool CSF, int TH, bool PH = false>
-static void launch_halo3(const ConvArgs& a, hipStream_t s) {
-  using HC = HaloCfg<TW, BN, TH>;
-  const int ntile = a.n_img * (a.H / HC::TH) * (a.W / TW) * ((a.N + BN - 1) / BN) * (PH ? 4 : 1);
-  LS_SET_MAX_DYN_SHM((conv3x3_halo_kernel<TW, BN, GN, CSF, TH, PH>), HC::SHM);
-  conv3x3_halo_kernel<TW, BN, GN, CSF, TH, PH><<<ntile, HC::NT, HC::SHM, s>>>(a);
-}
-
-template <int TW, int BN, int TH = 256 / TW>
-static void launch_halo2(const ConvArgs& a, hipStream_t s) {
-  if (a.aff_scale) {
-    if (a.cs_out) launch_halo3<TW, BN, true, true, TH>(a, s);
-    else launch_halo3<TW, BN, true, false, TH>(a, s);
-  } else {
-    if (a.cs_out) launch_halo3<TW, BN, false, true, TH>(a, s);
-    else launch_halo3<TW, BN, false, false, TH>(a, s);
-  }
-}
-
 // 16 x 8 patches, two blocks per CU for the 128-column tiles of convs with at most 4 input
 // chunks (Cin <= 256), where a block's halo prologue and epilogue are a large share of its
 // time: VAE 128 ch at 256^2 17.67 -> 17.23 ms, 128 -> 256 at 128^2 8.74 -> 8.43 ms, 256 at
@@ -2469,71 +2421,92 @@ static void launch_halo2(const ConvArgs& a, hipStream_t s) {
 // slots (13.12 -> 13.55 ms at 64^2), profiles/r05k_halo_ab.txt.  Tuning key 16 = 0: off.
 static bool g_halo_th8 = true;
 
-template <int TW>
-static void launch_halo1(const ConvArgs& a, hipStream_t s) {
-  if (a.N <= 16) launch_halo2<TW, 16, 8>(a, s);
-  else if (a.N % 160 == 0 && !(g_halo_bn128 && a.N % 128 == 0)) launch_halo2<TW, 160>(a, s);
-  else if (g_halo_th8 && a.H % 8 == 0 && a.Cin <= 256) launch_halo2<TW, 128, 8>(a, s);
-  else launch_halo2<TW, 128>(a, s);
+// whether the halo conv takes this call
+static bool halo_ok(const ls_conv_desc* d, const ConvArgs& a) {
+  if (!g_halo || g_force_tile || g_force_regstage || d->ksize != 3 || a.stride != 1 || a.pad != 1 ||
+      !a.ccm || a.Cin % 64 || a.C1 % 64 || a.K != (a.upsample == 2 ? 4 : 9) * a.Cin || a.y_f32 || a.act != LS_ACT_NONE ||
+      a.ln_mr || a.stats_out || a.ldy % 8 || (a.res && a.ldr % 8))
+    return false;
+  // nearest x2 upsample (Upsample3D, resnet.py:53-71; round 6): no input affine (the UNet's
+  // upsampler conv has none); the halo image is built in output space from the input pixels
+  if (a.upsample ? (!g_halo_ups || a.aff_scale || a.Ho != 2 * a.H || a.Wo != 2 * a.W) : (a.Ho != a.H || a.Wo != a.W))
+    return false;
+  // N <= 640: with more output channels the patch is re-loaded and re-transformed per N tile
+  // and the tiled 256x256 kernel wins (VAE 512 channels at 32^2: 3667 vs 3409 us; 128 at
+  // 256^2: 18660 vs 23610 us incl. the materialised GroupNorm; profiles/r04f_ab_t256_halo.txt)
+  // (N = 8 / 16: the narrow tile -- conv_out of the VAE decoder / encoder, N padded to 8)
+  const bool narrow = a.N % 8 == 0 && a.N <= 16 && a.H % 8 == 0 && g_halo_narrow;
+  if (((a.N % 160 && a.N % 128) || a.N > 640) && !narrow) return false;
+  if (a.aff_scale && (!a.silu_in || a.pix_per_sample % (a.H * a.W) || ((uintptr_t)a.aff_scale | (uintptr_t)a.aff_shift) & 15))
+    return false;  // (the kernel's input transform is the GroupNorm affine + SiLU of a ResnetBlock)
+  if (((uintptr_t)a.x1 | (uintptr_t)a.x2 | (uintptr_t)a.w) & 15 || a.ld1 % 8 || (a.C2 && a.ld2 % 8)) return false;
+  // 16 x 16 patches everywhere (the only patch width compiled): the smallest halo overhead
+  // ((16 + 2)^2 / 256 = 1.27 input pixels per output pixel; 32 x 8: 1.33, 64 x 4: 1.55) and no
+  // register spills (the phase form of an upsample conv, upsample == 2, patches the INPUT image)
+  if (a.upsample == 2 ? a.W % 16 || a.H % 16 : a.Wo % 16 || a.Ho % 16) return false;
+  if (a.upsample == 2 && (a.N <= 16 || a.C2)) return false;  // (no narrow tile, one source)
+  if ((long)a.H * a.W * a.ld1 * 2 >= (1L << 31) || (a.C2 && (long)a.H * a.W * a.ld2 * 2 >= (1L << 31)))
+    return false;  // per-image buffer descriptors
+  return true;
 }
 
-// the phase form (upsample == 2): input-space patches, the output parity a grid dimension;
-// the same tile choice as launch_halo1 (H, W here the input image)
-static void launch_halo_phase(const ConvArgs& a, hipStream_t s) {
-  ConvArgs o = a;
-  o.upsample = 0;  // (the kernel's halo image is the plain input-space one)
-  const bool cs = a.cs_out != nullptr;
-  if (a.N % 160 == 0 && !(g_halo_bn128 && a.N % 128 == 0)) {
-    if (cs) launch_halo3<16, 160, false, true, 16, true>(o, s);
-    else launch_halo3<16, 160, false, false, 16, true>(o, s);
-  } else if (g_halo_th8 && a.Cin <= 256) {
-    if (cs) launch_halo3<16, 128, false, true, 8, true>(o, s);
-    else launch_halo3<16, 128, false, false, 8, true>(o, s);
-  } else {
-    if (cs) launch_halo3<16, 128, false, true, 16, true>(o, s);
-    else launch_halo3<16, 128, false, false, 16, true>(o, s);
+// f(BN, TH) over the compiled halo tiles
+template <class F>
+static void with_halo_tile(const ls_conv_plan_info& i, F f) {
+  if (i.halo_bn == 16) f(IC<16>{}, IC<8>{});
+  else if (i.halo_bn == 160) f(IC<160>{}, IC<16>{});
+  else if (i.halo_th == 8) f(IC<128>{}, IC<8>{});
+  else f(IC<128>{}, IC<16>{});
+}
+
+// The halo kernel's arguments, tile and grid (halo_ok holds).  One tile choice for the plain
+// and the phase form (upsample == 2: input-space patches, the output parity a grid dimension).
+static void plan_halo(ConvPlan& p) {
+  ConvArgs& a = p.a;
+  ls_conv_plan_info& i = p.i;
+  i.halo_ph = a.upsample == 2;
+  i.family = i.halo_ph ? 4 : 3;
+  if (i.halo_ph) {
+    a.upsample = 0;  // (the kernel's halo image is the plain input-space one)
+  } else if (a.upsample) {  // the kernel works in output space: H, W = the output image
+    a.H = a.Ho;
+    a.W = a.Wo;
   }
+  i.halo_bn = a.N <= 16 ? 16 : (a.N % 160 == 0 && !(g_halo_bn128 && a.N % 128 == 0)) ? 160 : 128;
+  i.halo_th = i.halo_bn == 16 || (i.halo_bn == 128 && g_halo_th8 && a.Cin <= 256) ? 8 : 16;  // (H % 16 == 0)
+  i.halo_gn = a.aff_scale != nullptr;
+  i.halo_cs = a.cs_out != nullptr;
+  with_halo_tile(i, [&](auto bn, auto th) {
+    using HC = HaloCfg<16, decltype(bn)::value, decltype(th)::value>;
+    i.threads = HC::NT;
+    i.lds_bytes = (int)HC::SHM;
+  });
+  i.grid = a.n_img * (a.H / i.halo_th) * (a.W / 16) * cdiv(a.N, i.halo_bn) * (i.halo_ph ? 4 : 1);
 }
 
-static void launch_halo(const ConvArgs& a, int tw, hipStream_t s) {
-  (void)tw;  // (16: the only patch width compiled)
-  if (a.upsample == 2) {
-    launch_halo_phase(a, s);
-    return;
+template <int BN, int TH, bool PH>
+static void launch_halo2(const ConvPlan& p, hipStream_t s) {
+  if constexpr (!PH) {  // (the phase form takes no input affine)
+    if (p.i.halo_gn)
+      return p.i.halo_cs ? launch_plan<conv3x3_halo_kernel<16, BN, true, true, TH>>(p, s)
+                         : launch_plan<conv3x3_halo_kernel<16, BN, true, false, TH>>(p, s);
   }
-  if (a.upsample) {  // the kernel works in output space: H, W = the output image
-    ConvArgs o = a;
-    o.H = a.Ho;
-    o.W = a.Wo;
-    launch_halo1<16>(o, s);
-    return;
-  }
-  launch_halo1<16>(a, s);
+  p.i.halo_cs ? launch_plan<conv3x3_halo_kernel<16, BN, false, true, TH, PH>>(p, s)
+              : launch_plan<conv3x3_halo_kernel<16, BN, false, false, TH, PH>>(p, s);
 }
 
-
-// The phase form of an upsample conv (upsample == 2) on the tiled kernels, for what the halo
-// kernel does not take (N > 640, images its patches do not divide): per output parity a plain
-// pad-1 conv in input space over 4 of the 9 tap positions (BufDma's border masks and tap_of
-// as for any 3x3), the parity a grid slice, rows mapped to the strided output pixels in the
-// plain epilogue (EPI_PLAINP); GroupNorm column sums by the read pass over the stored output.
-static bool tiled_phase_ok(const ls_conv_desc* d, const ConvArgs& a, const TileCfg& t) {
-  const bool vec = (a.N % 8 == 0) && (a.ldy % 8 == 0) && (!a.res || a.ldr % 8 == 0);
-  return d->upsample == 2 && vec && !a.y_f32 && a.act == LS_ACT_NONE && !a.rowvec && !a.C2 && !g_force_regstage &&
-         buf_dma_ok(a, 3);
+static void launch_halo(const ConvPlan& p, hipStream_t s) {
+  with_halo_tile(p.i, [&](auto bn, auto th) {
+    constexpr int BN = decltype(bn)::value, TH = decltype(th)::value;
+    if constexpr (BN != 16) {  // (halo_ok: the phase form has no narrow tile)
+      if (p.i.halo_ph) return launch_halo2<BN, TH, true>(p, s);
+    }
+    launch_halo2<BN, TH, false>(p, s);
+  });
 }
 
-static void to_tiled_phase(ConvArgs& a, const TileCfg& t) {
-  a.phase = 1;  // (the kernel sets 1 + ph)
-  a.upsample = 0;
-  a.Ho = a.H;
-  a.Wo = a.W;
-  a.M = a.n_img * a.H * a.W;
-  a.ntm = cdiv(a.M, t.bm);
-  a.gm = std::max(1, std::min(a.gm, a.ntm));
-}
-
-static int build_args(const ls_conv_desc* d, ConvArgs& a, TileCfg& t, int& split) {
+// ---- the plan
+static int plan_conv(const ls_conv_desc* d, ConvPlan& p) {
   if (!d || !d->x1 || !d->w || !d->y) return fail(LS_ERR_INVALID, "ls_conv2d: null pointer");
   if (d->ksize != 1 && d->ksize != 3) return fail(LS_ERR_INVALID, "ls_conv2d: ksize must be 1 or 3");
   const int Cin = d->C1 + d->C2;
@@ -2546,7 +2519,7 @@ static int build_args(const ls_conv_desc* d, ConvArgs& a, TileCfg& t, int& split
     return fail(LS_ERR_INVALID, "ls_conv2d: upsample 2 (phase-packed weights) needs ksize 3, Cin % 64 == 0, K == 4 Cin, "
                                 "no affine prologue, stride 1, pad 1, Ho x Wo = 2H x 2W");
   const long Kneed = (d->upsample == 2 ? 4L : (long)d->ksize * d->ksize) * Cin;
-  if (d->K % 64 || d->K < Kneed || d->K - Kneed >= 64 + (d->ksize == 3 ? 0 : 0))
+  if (d->K % 64 || d->K < Kneed || d->K - Kneed >= 64)
     return fail(LS_ERR_INVALID, "ls_conv2d: K must be ksize^2*Cin rounded up to 64");
   if (d->ksize == 1 && (d->Ho != d->H || d->Wo != d->W || d->stride != 1 || d->upsample))
     return fail(LS_ERR_INVALID, "ls_conv2d: ksize 1 must be stride 1 with no resampling");
@@ -2559,6 +2532,8 @@ static int build_args(const ls_conv_desc* d, ConvArgs& a, TileCfg& t, int& split
   if (d->rowvec && d->rows_per_vec <= 0) return fail(LS_ERR_INVALID, "ls_conv2d: rowvec needs rows_per_vec");
   const long M = (long)d->n_img * d->Ho * d->Wo;
   if (M <= 0 || M >= (1L << 31)) return fail(LS_ERR_INVALID, "ls_conv2d: bad M");
+  p = ConvPlan{};
+  ConvArgs& a = p.a;
   a.x1 = d->x1; a.x2 = d->x2; a.C1 = d->C1; a.C2 = d->C2; a.Cin = Cin; a.ld1 = d->ld1; a.ld2 = d->ld2;
   a.n_img = d->n_img; a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo;
   a.stride = d->stride; a.pad = d->pad; a.upsample = d->upsample;
@@ -2580,10 +2555,10 @@ static int build_args(const ls_conv_desc* d, ConvArgs& a, TileCfg& t, int& split
     return fail(LS_ERR_INVALID, "ls_conv2d: gn_colsum_out needs M % 128 == 0, N % 8 == 0, bf16 output, no GEGLU");
   a.ablate = g_ablate;
   a.ccm = (d->ksize == 3 && Cin % 64 == 0) ? 1 : 0;
-  a.gm = 1;  // (set with the tile below)
   a.ktiles = d->K / 64;
-  t = pick_tile(M, d->N, a.ktiles, d->split_k <= 0 && d->workspace != nullptr && d->upsample != 2,
-                !d->aff_scale && !g_force_regstage && (d->ksize == 1 || Cin % 64 == 0), d->ksize);
+  // (automatic split-K only with a workspace; the phase forms have none)
+  TileCfg t = pick_tile(M, d->N, a.ktiles, d->split_k <= 0 && d->workspace != nullptr && d->upsample != 2,
+                        !d->aff_scale && !g_force_regstage && (d->ksize == 1 || Cin % 64 == 0), d->ksize);
   if (g_force_tile) {
     // (ids 7 and 8 were rejected 256-row variants; ls_set_tuning refuses them)
     static const int tb[10][2] = {{0, 0}, {128, 128}, {128, 64}, {64, 64}, {128, 32}, {256, 256}, {256, 128},
@@ -2603,12 +2578,69 @@ static int build_args(const ls_conv_desc* d, ConvArgs& a, TileCfg& t, int& split
   // sc2b -1 %, profiles/r05s_gm_ab.txt; at K = 5120 the grouping loses)
   if (t.bm == 256 && t.bn == 256 && d->ksize == 1 && d->K <= 1920) a.gm = 4;
   a.gm = std::max(1, std::min(a.gm, a.ntm));
-  split = d->upsample == 2 ? 1 : d->split_k > 0 ? d->split_k : t.split;  // (the phase forms have no split-K)
-  split = std::min(split, a.ktiles);
-  a.kt_per_split = cdiv(a.ktiles, split);
-  split = cdiv(a.ktiles, a.kt_per_split);
-  a.split = split;
-  a.partial = nullptr;
+  set_split(a, d->upsample == 2 ? 1 : d->split_k > 0 ? d->split_k : t.split);
+  const size_t slab = (size_t)a.M * a.N * sizeof(float);
+  ls_conv_plan_info& i = p.i;
+  i.bm = i.bn = i.ks = i.tapu = i.buf = i.epi = i.rb_kt = i.rb_fm = i.rb_flags = -1;
+  i.halo_bn = i.halo_th = i.halo_gn = i.halo_cs = i.halo_ph = -1;
+  i.workspace_bytes = a.split > 1 ? (int64_t)(a.split * slab) : 0;
+  // fewer splits where the workspace does not hold them all
+  if (a.split > 1 && (!d->workspace || d->workspace_bytes < a.split * slab))
+    set_split(a, d->workspace ? (int)std::min<size_t>(d->workspace_bytes / slab, a.split) : 1);
+  if (a.split > 1) a.partial = (float*)d->workspace;
+
+  // ---- the kernel: the order of these rounds is the behaviour
+  float* const cs = a.cs_out;        // GroupNorm column sums: a kernel's epilogue, else a read pass over y
+  float* const stats = a.stats_out;  // LayerNorm row statistics: the row-block epilogue, else ls_row_stats over y
+  bool planned = false;
+  if (halo_ok(d, a)) {  // 3x3 from an LDS halo tile: input affine and column sums fused; its phase form
+    plan_halo(p);
+    planned = true;
+  } else if (a.upsample == 2) {  // the phase form on the tiled kernels
+    if (!tiled_phase_ok(a))
+      return fail(LS_ERR_INVALID, "ls_conv2d: no phase-form kernel for this shape (ls_conv_path -1): use upsample = 1");
+    to_tiled_phase(a, t.bm);
+  } else if (rowblock_ok(d, a)) {
+    // (statistics, column sums) in the row-block epilogue: both, then the sums by the read
+    // pass, then the statistics by ls_row_stats with the sums fused, then neither
+    for (int round = 0; round < 4 && !planned; ++round) {
+      const bool fuse_stats = round < 2, fuse_cs = round % 2 == 0;
+      if ((!fuse_stats && !stats) || (!fuse_cs && !cs)) continue;  // (an earlier round already asked this)
+      a.stats_out = fuse_stats ? stats : nullptr;
+      a.cs_out = fuse_cs ? cs : nullptr;
+      planned = plan_rowblock(p);
+    }
+    if (planned) {
+      p.cs_pass = a.cs_out ? nullptr : cs;
+      p.row_stats = a.stats_out ? nullptr : stats;
+    }
+  }
+  if (!planned) {  // the tiled kernels
+    const bool regstage = a.aff_scale || g_force_regstage;  // the prologue needs the register path
+    // epilogue column sums: single-pass vectorised epilogue and a tile whose staging
+    // buffer holds the per-thread partials (cs_tile_fits; not 128x32 / 64x64)
+    // (not the 256-row kernels: compiled in, the sums cost their main loop ~12 % -- they run
+    // at the 256-VGPR limit -- against a ~15 us read pass; same-box A/B, scripts/ab_lib.sh)
+    const bool cs_epi = cs && !a.phase && a.split == 1 && vec_ok(a) && !(t.bm == 128 && t.bn == 32) && t.bm != 64 && t.bm < 256;
+    a.cs_out = cs_epi ? cs : nullptr;
+    a.stats_out = nullptr;
+    p.cs_pass = cs_epi ? nullptr : cs;
+    p.row_stats = stats;
+    i.family = a.phase ? 5 : regstage ? 2 : 0;
+    i.bm = t.bm;
+    i.bn = t.bn;
+    i.ks = d->ksize;
+    i.tapu = d->ksize == 3 && Cin % 64 == 0;
+    i.buf = !regstage && buf_dma_ok(a, d->ksize);
+    i.epi = regstage ? -1 : epi_kind(a);
+    i.grid = a.ntm * a.ntn * (a.phase ? 4 : a.split);
+    i.threads = t.bm == 256 ? 512 : 256;
+    i.lds_bytes = regstage ? 0 : (int)tiled_lds(t.bm, t.bn, t.bn == 32 ? 4 : 2);
+    i.reduce = a.split > 1;
+  }
+  i.split = a.split;
+  i.colsum_rows = p.cs_pass ? a.Mo : 0;
+  i.row_stats = p.row_stats != nullptr;
   return LS_OK;
 }
 
@@ -2659,103 +2691,51 @@ static int occ(K kern, int threads, size_t shm) {
 
 extern "C" int ls_gemm_occupancy(int32_t which) {
   switch (which) {
-    case 1: return occ(conv_gemm_dma_kernel<128, 160, 2, 2, 1, false, EPI_PLAIN>, 256,
-                       (size_t)2 * (128 + 160) * 8 * 16);
-    case 2: return occ(conv_gemm_big_kernel<256, 1, false, EPI_PLAIN>, 512, (size_t)2 * (256 + 256) * 8 * 16);
-    case 3: return occ(conv_gemm_dma_kernel<128, 128, 2, 2, 1, false, EPI_PLAIN>, 256,
-                       (size_t)2 * (128 + 128) * 8 * 16);
+    case 1: return occ(conv_gemm_dma_kernel<128, 160, 2, 2, 1, false, EPI_PLAIN>, 256, tiled_lds(128, 160, 2));
+    case 2: return occ(conv_gemm_big_kernel<256, 1, false, EPI_PLAIN>, 512, tiled_lds(256, 256, 2));
+    case 3: return occ(conv_gemm_dma_kernel<128, 128, 2, 2, 1, false, EPI_PLAIN>, 256, tiled_lds(128, 128, 2));
     default: return fail(LS_ERR_INVALID, "ls_gemm_occupancy: which 1..3");
   }
 }
 
+extern "C" int ls_conv_plan(const ls_conv_desc* d, ls_conv_plan_info* out) {
+  ConvPlan p;
+  if (!out) return fail(LS_ERR_INVALID, "ls_conv_plan: null out");
+  const int rc = plan_conv(d, p);
+  if (rc == LS_OK) *out = p.i;
+  return rc;
+}
+
+extern "C" int ls_conv_path(const ls_conv_desc* d) {
+  ConvPlan p;
+  return plan_conv(d, p) == LS_OK ? p.i.family : -1;
+}
+
 extern "C" size_t ls_conv_workspace_bytes(const ls_conv_desc* d) {
-  ConvArgs a; TileCfg t; int split;
-  if (build_args(d, a, t, split) != LS_OK) return 0;
-  return split > 1 ? (size_t)split * a.M * a.N * sizeof(float) : 0;
+  ConvPlan p;  // (the bytes are taken before the split is fitted: the plan of an unlimited workspace)
+  return plan_conv(d, p) == LS_OK ? (size_t)p.i.workspace_bytes : 0;
 }
 
 extern "C" int ls_conv2d(const ls_conv_desc* d, void* stream) {
-  ConvArgs a; TileCfg t; int split;
-  int rc = build_args(d, a, t, split);
+  ConvPlan p;
+  int rc = plan_conv(d, p);
   if (rc != LS_OK) return rc;
-  if (split > 1) {
-    const size_t need = (size_t)split * a.M * a.N * sizeof(float);
-    if (!d->workspace || d->workspace_bytes < need) {
-      // fall back to fewer splits that fit the workspace
-      const size_t per = (size_t)a.M * a.N * sizeof(float);
-      int fit = d->workspace ? (int)(d->workspace_bytes / per) : 0;
-      if (fit < 2) { split = 1; } else { split = std::min(split, fit); }
-      a.kt_per_split = cdiv(a.ktiles, split);
-      split = cdiv(a.ktiles, a.kt_per_split);
-      a.split = split;
-    }
-    if (split > 1) a.partial = (float*)d->workspace;
-  }
   hipStream_t s = (hipStream_t)stream;
-  const bool tphase = a.upsample == 2 && !halo_tw(d, a);
-  if (tphase) {  // the phase form on the tiled kernels (callers ask ls_conv_path first: 5)
-    if (!tiled_phase_ok(d, a, t))
-      return fail(LS_ERR_INVALID, "ls_conv2d: no phase-form kernel for this shape (ls_conv_path -1): use upsample = 1");
-    to_tiled_phase(a, t);
-  }
-  if (const int tw = tphase ? 0 : halo_tw(d, a)) {  // 3x3 from an LDS halo tile, input affine fused, with the column sums
-    launch_halo(a, tw, s);
-    return check_launch("conv3x3_halo_kernel");
-  }
-  float* cs = a.cs_out;  // GroupNorm column sums: epilogue (tiled / row-block) or a trailing read pass
-  if (!tphase && rowblock_ok(d, a)) {
-    if (launch_rowblock(a, s)) return check_launch("gemm_rowblock_kernel");  // with cs_out if given
-    a.cs_out = nullptr;  // no row-block instance with the sums: without them, then a read pass
-    if (cs && launch_rowblock(a, s)) {
-      if ((rc = check_launch("gemm_rowblock_kernel")) != LS_OK) return rc;
-      return launch_colsum_pass((const u16*)d->y, d->ldy, a.M, d->N, cs, s);
-    }
-  }
-  a.cs_out = nullptr;
-  if (a.stats_out) {  // tiled path: the GEMM, then LayerNorm statistics of y in a second pass
-    float* so = a.stats_out;
-    a.stats_out = nullptr;
-    ls_conv_desc d2 = *d;
-    d2.row_stats_out = nullptr;
-    if ((rc = ls_conv2d(&d2, stream)) != LS_OK) return rc;
-    return ls_row_stats((const uint16_t*)d->y, d->ldy, a.M, d->N, a.stats_eps, so, stream);
-  }
-  const bool tapu = (d->ksize == 3) && (a.Cin % 64 == 0);
-  const int grid = a.ntm * a.ntn * (tphase ? 4 : a.split);
-  // epilogue column sums: single-pass vectorised epilogue and a tile whose staging
-  // buffer holds the per-thread partials (cs_tile_fits; not 128x32 / 64x64)
-  const bool vec = (a.N % 8 == 0) && (a.ldy % 8 == 0) && (!a.res || a.ldr % 8 == 0);
-  // (not the 256-row kernels: compiled in, the sums cost their main loop ~12 % -- they run
-  // at the 256-VGPR limit -- against a ~15 us read pass; same-box A/B, scripts/ab_lib.sh)
-  const bool cs_epi = cs && !tphase && a.split == 1 && vec && !(t.bm == 128 && t.bn == 32) && t.bm != 64 && t.bm < 256;
-  if (cs_epi) a.cs_out = cs;
-  if (t.bm == 256 && !a.aff_scale && !g_force_regstage) {
-    if (t.bn == 256) launch_big<256>(a, d->ksize, tapu, grid, s);
-    else launch_big<128>(a, d->ksize, tapu, grid, s);
-  } else if (t.bm == 128 && t.bn == 128) launch_cfg<128, 128, 2, 2>(a, d->ksize, tapu, grid, s);
-  else if (t.bm == 128 && t.bn == 160) launch_cfg<128, 160, 2, 2>(a, d->ksize, tapu, grid, s);
-  else if (t.bm == 128 && t.bn == 64) launch_cfg<128, 64, 2, 2>(a, d->ksize, tapu, grid, s);
-  else if (t.bm == 128 && t.bn == 32) launch_cfg<128, 32, 4, 1>(a, d->ksize, tapu, grid, s);
-  else launch_cfg<64, 64, 2, 2>(a, d->ksize, tapu, grid, s);
-  if ((rc = check_launch("conv_gemm_kernel")) != LS_OK) return rc;
-  if (a.split > 1) {
+  const ConvArgs& a = p.a;
+  const int f = p.i.family;
+  if (f == 1) launch_rowblock(p, s, RowblockInstances{});
+  else if (f == 3 || f == 4) launch_halo(p, s);
+  else launch_tiled(p, s);
+  rc = check_launch(f == 1 ? "gemm_rowblock_kernel" : f == 3 || f == 4 ? "conv3x3_halo_kernel" : "conv_gemm_kernel");
+  if (rc != LS_OK) return rc;
+  if (p.i.reduce) {
     const long nchunk = (long)a.M * ((((a.act == LS_ACT_GEGLU) ? a.N / 2 : a.N) + 7) / 8);
     splitk_reduce_kernel<<<cdiv(nchunk, 256), 256, 0, s>>>(a);
     if ((rc = check_launch("splitk_reduce_kernel")) != LS_OK) return rc;
   }
-  if (cs && !cs_epi) return launch_colsum_pass((const u16*)d->y, d->ldy, a.Mo, d->N, cs, s);
+  if (p.cs_pass && (rc = launch_colsum_pass((const u16*)a.y, a.ldy, p.i.colsum_rows, a.N, p.cs_pass, s)) != LS_OK) return rc;
+  if (p.row_stats) return ls_row_stats((const uint16_t*)a.y, a.ldy, a.Mo, a.N, a.stats_eps, p.row_stats, stream);
   return LS_OK;
-}
-
-extern "C" int ls_conv_path(const ls_conv_desc* d) {
-  ConvArgs a; TileCfg t; int split;
-  if (build_args(d, a, t, split) != LS_OK) return -1;
-  a.cs_out = nullptr;  // (the column sums never change the path)
-  if (a.upsample == 2) return halo_tw(d, a) ? 4 : tiled_phase_ok(d, a, t) ? 5 : -1;
-  int ntm, ntn;
-  if (rowblock_ok(d, a) && rowblock_flags(a, &ntm, &ntn) >= 0) return 1;
-  if (halo_tw(d, a)) return 3;
-  return (a.aff_scale || g_force_regstage) ? 2 : 0;
 }
 
 extern "C" int ls_gn_colsum(const uint16_t* y, int64_t ldy, int64_t M, int32_t N, float* out, void* stream) {

@@ -80,12 +80,20 @@ def conv_path(x, pw: Packed, **kw):
     """Which kernel family ls_conv2d takes for this call (ls_conv_path: 0 tiled, 1 row-block,
     2 register-staged, 3 halo-tile 3x3, 4 / 5 the halo-tile / tiled phase form of an upsample
     conv) -- host only, nothing is launched."""
-    return conv(x, pw, _path_only=True, **kw)
+    return conv(x, pw, _query="path", **kw)
+
+
+def conv_plan(x, pw: Packed, **kw):
+    """The plan ls_conv2d makes for this call (ls_conv_plan), as a dict of the integers of
+    ls_conv_plan_info: family (= conv_path), kernel instance, launch geometry, trailing passes
+    -- host only, nothing is launched.  None where the library refuses the descriptor
+    (_lib.load().ls_last_error() has the reason)."""
+    return conv(x, pw, _query="plan", **kw)
 
 
 def conv(x, pw: Packed, *, x2=None, aff=None, stride=1, pad=None, upsample=False, out_hw=None, rowvec=None,
          res=None, out_scale=1.0, act=ACT_NONE, out=None, out_f32=False, split_k=0, ln_stats=None,
-         stats_out=None, gn_out=False, aff_materialize=False, _path_only=False):
+         stats_out=None, gn_out=False, aff_materialize=False, workspace_bytes=None, _query=None):
     """Fused conv/linear.  x (n, H, W, C1) [+ x2 (n, H, W, C2)] -> (n, Ho, Wo, n_out).
     aff = (scale[S][C], shift[S][C], imgs_per_sample, silu); rowvec = (t[S][ld], rows_per_vec, ld[, mod]);
     ln_stats = (mean, rstd) rows from row_stats(): LayerNorm folded into pw (pw.colsum);
@@ -96,7 +104,9 @@ def conv(x, pw: Packed, *, x2=None, aff=None, stride=1, pad=None, upsample=False
     attached to the result as `.gn_cs` for group_norm() (when rows % 128 == 0);
     aff_materialize = when the call would take the register-staged GEMM for the affine
     prologue (ls_conv_path 2), apply it with ls_groupnorm_apply first instead (the
-    row-block GEMM folds it into its register-resident A rows)."""
+    row-block GEMM folds it into its register-resident A rows);
+    workspace_bytes = a cap on the split-K workspace of this call (0: none; default: all of it,
+    handed over with the launch -- conv_path / conv_plan then answer for a call without one)."""
     lib = _lib.load()
     n, H, W, C1 = x.shape
     C2 = x2.shape[3] if x2 is not None else 0
@@ -137,6 +147,8 @@ def conv(x, pw: Packed, *, x2=None, aff=None, stride=1, pad=None, upsample=False
     assert tuple(out.shape) == (n, Ho, Wo, n_out), (tuple(out.shape), (n, Ho, Wo, n_out))
     d.y, d.ldy, d.y_f32 = _p(out), _ld(out), int(out.dtype == torch.float32)
     d.split_k = split_k
+    if workspace_bytes:
+        d.workspace, d.workspace_bytes = _p(ws.gemm), min(workspace_bytes, ws.gemm.numel())
     if stats_out is not None:
         assert stats_out.dtype == torch.float32 and stats_out.is_contiguous() and stats_out.numel() == 2 * n * Ho * Wo
         assert pw.n_out == pw.N and act != ACT_GEGLU, "row statistics over the real output channels only"
@@ -147,19 +159,28 @@ def conv(x, pw: Packed, *, x2=None, aff=None, stride=1, pad=None, upsample=False
         d.upsample, d.w, d.K = 2, _p(pw.phase), pw.phase.shape[2]
         if lib.ls_conv_path(C.byref(d)) not in (4, 5):
             d.upsample, d.w, d.K = 1, _p(pw.w), pw.K
-    if _path_only:
-        return lib.ls_conv_path(C.byref(d))
-    if aff is not None and aff_materialize and lib.ls_conv_path(C.byref(d)) == 2:
+    if aff is not None and aff_materialize and not _query and lib.ls_conv_path(C.byref(d)) == 2:
         xa = group_norm_apply(x, aff[0], aff[1], n // aff[2], bool(aff[3]), x2=x2)
         return conv(xa, pw, stride=stride, pad=pad, upsample=upsample, out_hw=out_hw, rowvec=rowvec, res=res,
                     out_scale=out_scale, act=act, out=out, out_f32=out_f32, split_k=split_k, ln_stats=ln_stats,
-                    stats_out=stats_out, gn_out=gn_out)
+                    stats_out=stats_out, gn_out=gn_out, workspace_bytes=workspace_bytes)
     cs = None
     if gn_out and _GN_EPILOGUE and (n * Ho * Wo) % GN_SLOT_ROWS == 0 and out.dtype == torch.bfloat16 and act != ACT_GEGLU:
         assert pw.n_out == pw.N
         cs = torch.empty((n * Ho * Wo // GN_SLOT_ROWS, 2, n_out), dtype=torch.float32, device=x.device)
         d.gn_colsum_out = _p(cs)
-    d.workspace, d.workspace_bytes = _p(ws.gemm), ws.gemm.numel()
+    # the questions are asked without the split-K workspace unless workspace_bytes names one:
+    # the library splits K on its own only where it has a workspace, so a shape it would split
+    # (few tiles, deep K) is answered here as unsplit
+    if _query == "path":
+        return lib.ls_conv_path(C.byref(d))
+    if _query == "plan":
+        info = _lib.ConvPlanInfo()
+        if lib.ls_conv_plan(C.byref(d), C.byref(info)) != 0:
+            return None
+        return {f: getattr(info, f) for f, _ in info._fields_}
+    if workspace_bytes is None:
+        d.workspace, d.workspace_bytes = _p(ws.gemm), ws.gemm.numel()
     check(lib.ls_conv2d(C.byref(d), _stream()), "ls_conv2d")
     if cs is not None:
         out.gn_cs = cs
