@@ -721,6 +721,65 @@ int ls_face_brighten(uint8_t* frames, int32_t n, int32_t H, int32_t W, const int
                      const float* taps, int32_t n_taps, int32_t dilate, float c, int32_t brighten, int32_t max_value,
                      int32_t frames_per_batch, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- StableSyncNet sync confidence (additive, ABI stays 14) --------------------------- */
+
+/* The reference's SyncNet mel front end (latentsync/utils/audio.py:59-65 with
+ * configs/audio.yaml), a different transform from ls_log_mel's Whisper one: audio fp32 mono
+ * 16 kHz [n] -> out fp32 [T][80] frame-major, T = 1 + n / 200.  In this order:
+ * pre-emphasis y[0] = x[0], y[i] = x[i] - 0.97 x[i-1]; STFT n_fft = win = 800, hop 200,
+ * periodic Hann, centred with 400 ZEROS each side (librosa 0.10.1's default pad_mode);
+ * magnitude; filters fp32 [80][401] (latentsync_amd.syncnet.mel_filters); S = 20 log10(max(
+ * 1e-5, .)) - 20; clip(8 (S + 100) / 100 - 4, -4, 4).  fp32 throughout, a direct DFT
+ * against a twiddle table.  One launch, no workspace.  LS_ERR_INVALID, nothing launched:
+ * null pointers, n < 1 or above 2^38 (the frame count stays in int32). */
+int ls_syncnet_mel(const float* audio, int64_t n, const float* filters, float* out, void* stream);
+
+/* SyncNetDataset's visual input (syncnet_dataset.py, lower_half) from the pipeline's
+ * aligned faces: faces uint8 [n][R][R][3] (run_windows' out_u8) -> out bf16
+ * [B][R/2][R][3 F].  Window b holds frames starts[b] .. starts[b] + F - 1 (starts int32 [B]
+ * on the device), rows R/2 .. R-1, channel 3 f + c ("b f c h w -> b (f c) h w"), value
+ * (x / 255 - 0.5) / 0.5 in fp32 with an IEEE division, rounded to bf16.  The host checks
+ * the starts; a window that leaves [0, n) is written as zeros and never read.
+ * LS_ERR_INVALID: null pointers, n or B < 1, R odd, F < 1 or > n, 3 F % 8 != 0. */
+int ls_syncnet_pack_frames(const uint8_t* faces, int32_t n, int32_t R, const int32_t* starts, int32_t B, int32_t F,
+                           uint16_t* out, void* stream);
+
+/* The audio encoder's input: mel fp32 [T][80] (ls_syncnet_mel) -> out bf16 [B][80][L][8],
+ * channel 0 = mel[cols[b] + j][m] at pixel (m, j), channels 1..7 zero (the 1-channel conv_in
+ * then runs on ls_conv2d with zero weight columns); cols int32 [B] on the device.  The host
+ * checks cols[b] + L <= T; a column outside [0, T) is written as zero and never read.
+ * LS_ERR_INVALID: null pointers, T, B or L < 1, L > T. */
+int ls_syncnet_pack_mel(const float* mel, int32_t T, const int32_t* cols, int32_t B, int32_t L, uint16_t* out,
+                        void* stream);
+
+/* 3x3 convolution with one stride per axis and one-sided zero padding -- ResnetBlock2D's
+ * anisotropic downsamplers (stable_syncnet.py:95-109, 129-131: F.pad then stride [1,2],
+ * [2,1] or [2,3], padding 0) -- as an implicit GEMM on v_mfma_f32_16x16x32_bf16, fp32
+ * accumulate: x bf16 NHWC [n_img][H][W] pitch ldx, y bf16 [n_img][Ho][Wo] pitch ldy,
+ *   y[img, oy, ox, n] = bias[n] + sum_{ky, kx, ci} x[img, oy stride_h - pad_top + ky,
+ *                                                   ox stride_w - pad_left + kx, ci] w[n, ky, kx, ci]
+ * where a tap outside the image on ANY side reads zero (so Ho, Wo say how far the bottom /
+ * right padding reaches).  w is ls_conv2d's packed 3x3 operand [N][K], K = 9 Cin rounded up
+ * to 64, in the same two k orders (packing.pack_weight); bias fp32 [N] or NULL.  Any
+ * M = n_img Ho Wo (also below 16) and any N.  A result does not depend on n_img: the kernel
+ * form is chosen from K and N alone.  LS_ERR_INVALID, nothing launched: null x / w / y,
+ * a stride outside 1..3, a pad outside 0..1, Cin % 8, ldx % 8, ldy % 8, ldx < Cin, ldy < N,
+ * K not that of Cin, an output pixel whose first tap row or column is outside the image,
+ * pointers not 16-byte aligned. */
+int ls_conv3x3_strided(const uint16_t* x, int32_t ldx, int32_t n_img, int32_t H, int32_t W, int32_t Cin,
+                       const uint16_t* w, int32_t K, int32_t N, const float* bias, int32_t stride_h,
+                       int32_t stride_w, int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo, uint16_t* y,
+                       int32_t ldy, void* stream);
+
+/* StableSyncNet.forward's tail and the score (stable_syncnet.py:55-60, 230-231): v_in, a_in
+ * bf16 [B][D] (pitches ldv, lda): the encoders' norm_out outputs before the ReLU.  In fp32:
+ * ReLU, x / max(|x|_2, 1e-12) (F.normalize) -> v, a fp32 [B][D] pitch ldo, and
+ * score[b] = v . a / (max(|v|, 1e-8) max(|a|, 1e-8)) (F.cosine_similarity).  An all-negative
+ * embedding gives a zero vector and score 0.  LS_ERR_INVALID: null pointers, B or D < 1,
+ * a pitch below D. */
+int ls_sync_score(const uint16_t* v_in, int32_t ldv, const uint16_t* a_in, int32_t lda, int32_t B, int32_t D,
+                  float* v, float* a, int32_t ldo, float* score, void* stream);
+
 int ls_abi_version(void);
 const char* ls_last_error(void);
 

@@ -150,6 +150,14 @@ _SIGS = {
                                    C.c_int32, C.c_int32, C.c_int32, c_vp, C.c_int32, C.c_int32, C.c_float, C.c_int32,
                                    C.c_int32, C.c_int32, c_vp, C.c_size_t, c_vp]),
     "ls_add_rows":(C.c_int, [c_vp, C.c_int64, C.c_int32, C.c_int32, c_vp, C.c_int32, c_vp, C.c_int32, c_vp]),
+    "ls_syncnet_mel": (C.c_int, [c_vp, C.c_int64, c_vp, c_vp, c_vp]),
+    "ls_syncnet_pack_frames": (C.c_int, [c_vp, C.c_int32, C.c_int32, c_vp, C.c_int32, C.c_int32, c_vp, c_vp]),
+    "ls_syncnet_pack_mel": (C.c_int, [c_vp, C.c_int32, c_vp, C.c_int32, C.c_int32, c_vp, c_vp]),
+    "ls_conv3x3_strided": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_vp, C.c_int32,
+                                     C.c_int32, c_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, c_vp, C.c_int32, c_vp]),
+    "ls_sync_score": (C.c_int, [c_vp, C.c_int32, c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, c_vp, C.c_int32, c_vp,
+                                c_vp]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -722,6 +722,104 @@ def paste_back(dec, pix, mask, out_nchw=None, out_u8=None):
                             _p(out_u8), _stream()), "ls_paste_back")
 
 
+def conv3x3_strided(x, pw: Packed, stride, pad, out_hw, out=None):
+    """3x3 conv with per-axis strides and one-sided zero padding (ls_conv3x3_strided):
+    x (n, H, W, Cin) bf16 NHWC -> (n, Ho, Wo, N) bf16; stride = (sh, sw) in 1..3, pad =
+    (top, left) in 0..1, out_hw = (Ho, Wo) -- taps past the bottom / right edge read zero.
+    pw is the ordinary packed 3x3 operand.  ``out`` may be a pitched NHWC view."""
+    lib = _lib.load()
+    n, H, W, Cin = x.shape
+    assert pw.ksize == 3 and pw.cin == Cin, (pw.ksize, pw.cin, Cin)
+    Ho, Wo = out_hw
+    if out is None:
+        out = torch.empty((n, Ho, Wo, pw.N), dtype=torch.bfloat16, device=x.device)
+    assert tuple(out.shape) == (n, Ho, Wo, pw.N) and out.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
+    check(lib.ls_conv3x3_strided(_p(x), _ld(x), n, H, W, Cin, _p(pw.w), pw.K, pw.N, _p(pw.bias), stride[0], stride[1],
+                                 pad[0], pad[1], Ho, Wo, _p(out), _ld(out), _stream()), "ls_conv3x3_strided")
+    return out
+
+
+def syncnet_mel(wav, filters, out=None):
+    """SyncNet mel front end (ls_syncnet_mel): wav fp32 (n,) at 16 kHz, filters fp32 (80, 401),
+    both on the device -> fp32 (T, 80) frame-major, T = 1 + n // 200."""
+    lib = _lib.load()
+    if wav.dim() != 1 or wav.dtype != torch.float32 or not wav.is_cuda or not wav.is_contiguous() or wav.numel() < 1:
+        raise ValueError(f"syncnet_mel: a non-empty contiguous fp32 1-D device tensor expected, got {wav.dtype} "
+                         f"{tuple(wav.shape)} on {wav.device}")
+    assert tuple(filters.shape) == (80, 401) and filters.dtype == torch.float32 and filters.is_contiguous()
+    T = 1 + wav.numel() // 200
+    if out is None:
+        out = torch.empty((T, 80), dtype=torch.float32, device=wav.device)
+    assert tuple(out.shape) == (T, 80) and out.is_contiguous() and out.dtype == torch.float32
+    check(lib.ls_syncnet_mel(_p(wav), wav.numel(), _p(filters), _p(out), _stream()), "ls_syncnet_mel")
+    return out
+
+
+def syncnet_pack_frames(faces_u8, starts, num_frames, out=None):
+    """uint8 faces (n, R, R, 3) on the device + frame starts (host ints) -> the visual
+    encoder's input (B, R/2, R, 3 num_frames) bf16: lower half, channel 3 f + c, (x / 255 -
+    0.5) / 0.5 (ls_syncnet_pack_frames).  A window outside the frames raises here."""
+    lib = _lib.load()
+    if faces_u8.dtype != torch.uint8 or faces_u8.dim() != 4 or faces_u8.shape[3] != 3 or \
+            faces_u8.shape[1] != faces_u8.shape[2] or not faces_u8.is_cuda or not faces_u8.is_contiguous():
+        raise ValueError(f"syncnet_pack_frames: contiguous uint8 (n, R, R, 3) on the device expected, got "
+                         f"{faces_u8.dtype} {tuple(faces_u8.shape)} on {faces_u8.device}")
+    n, R = faces_u8.shape[0], faces_u8.shape[1]
+    starts = [int(s) for s in starts]
+    F_ = int(num_frames)
+    if not starts or min(starts) < 0 or max(starts) + F_ > n:
+        raise ValueError(f"syncnet_pack_frames: windows {starts} of {F_} frames do not lie in {n} frames")
+    if R % 2 or F_ < 1 or (3 * F_) % 8:
+        raise ValueError(f"syncnet_pack_frames: R = {R} must be even and 3 * num_frames = {3 * F_} a multiple of 8")
+    B = len(starts)
+    st = torch.tensor(starts, dtype=torch.int32, device=faces_u8.device)
+    if out is None:
+        out = torch.empty((B, R // 2, R, 3 * F_), dtype=torch.bfloat16, device=faces_u8.device)
+    assert tuple(out.shape) == (B, R // 2, R, 3 * F_) and out.is_contiguous() and out.dtype == torch.bfloat16
+    check(lib.ls_syncnet_pack_frames(_p(faces_u8), n, R, _p(st), B, F_, _p(out), _stream()), "ls_syncnet_pack_frames")
+    return out
+
+
+def syncnet_pack_mel(mel, cols, mel_len=52, out=None):
+    """mel fp32 (T, 80) on the device + window columns (host ints) -> the audio encoder's
+    input (B, 80, mel_len, 8) bf16, channel 0 = mel[cols[b] + j][m], channels 1..7 zero
+    (ls_syncnet_pack_mel).  A window past the end of the mel raises here."""
+    lib = _lib.load()
+    if mel.dtype != torch.float32 or mel.dim() != 2 or mel.shape[1] != 80 or not mel.is_cuda or not mel.is_contiguous():
+        raise ValueError(f"syncnet_pack_mel: contiguous fp32 (T, 80) on the device expected, got {mel.dtype} "
+                         f"{tuple(mel.shape)} on {mel.device}")
+    T, L = mel.shape[0], int(mel_len)
+    cols = [int(c) for c in cols]
+    if not cols or L < 1 or min(cols) < 0 or max(cols) + L > T:
+        raise ValueError(f"syncnet_pack_mel: windows {cols} of {L} columns do not lie in {T} mel frames")
+    B = len(cols)
+    ct = torch.tensor(cols, dtype=torch.int32, device=mel.device)
+    if out is None:
+        out = torch.empty((B, 80, L, 8), dtype=torch.bfloat16, device=mel.device)
+    assert tuple(out.shape) == (B, 80, L, 8) and out.is_contiguous() and out.dtype == torch.bfloat16
+    check(lib.ls_syncnet_pack_mel(_p(mel), T, _p(ct), B, L, _p(out), _stream()), "ls_syncnet_pack_mel")
+    return out
+
+
+def sync_score(v_in, a_in, v=None, a=None, score=None):
+    """ReLU + F.normalize of both embeddings and their cosine (ls_sync_score): v_in, a_in
+    bf16 (B, D) rows (row-strided views allowed) -> (v, a fp32 (B, D), score fp32 (B,))."""
+    lib = _lib.load()
+    B, D = v_in.shape
+    assert tuple(a_in.shape) == (B, D) and v_in.dtype == a_in.dtype == torch.bfloat16
+    assert v_in.stride(1) == 1 and a_in.stride(1) == 1
+    if v is None:
+        v = torch.empty((B, D), dtype=torch.float32, device=v_in.device)
+    if a is None:
+        a = torch.empty((B, D), dtype=torch.float32, device=v_in.device)
+    if score is None:
+        score = torch.empty((B,), dtype=torch.float32, device=v_in.device)
+    assert v.stride(1) == 1 and a.stride(1) == 1 and v.stride(0) == a.stride(0) and score.is_contiguous()
+    check(lib.ls_sync_score(_p(v_in), v_in.stride(0) if B > 1 else D, _p(a_in), a_in.stride(0) if B > 1 else D, B, D,
+                            _p(v), _p(a), v.stride(0) if B > 1 else D, _p(score), _stream()), "ls_sync_score")
+    return v, a, score
+
+
 def add_rows(x2d, table, out=None):
     lib = _lib.load()
     rows, C_ = x2d.shape

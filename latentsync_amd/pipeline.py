@@ -527,7 +527,10 @@ class LipsyncPipeline:
         (N, P, 2) array of FaceMesh's normalised (x, y), one row per frame of data.pth, NaN
         where no face was detected.  With
         ``faces_only=True`` (or a video_path that is not an array file) the
-        lip-synced aligned faces are written instead and no warp-back happens."""
+        lip-synced aligned faces are written instead and no warp-back happens.
+        ``syncnet=`` (a syncnet.StableSyncNet on this device) scores the synced faces against
+        the audio after the window loop (sync_confidence): last_sync_scores / last_sync_conf are
+        set and an .npz output gains ``sync_scores`` and ``sync_conf``; an .avi is unchanged."""
         from . import repeat as rep
         # write_video's brightness restore runs only `if use_darken and brightness_factor`
         # (util.py:150-151, reached from :594).  It runs on the device (darken.py) from the
@@ -612,6 +615,9 @@ class LipsyncPipeline:
                                        generator, callback=callback, callback_steps=callback_steps, height=R)
         if not rank0:
             return None  # rank 0 restores and writes the gathered clip
+        sync = None
+        if kwargs.get("syncnet") is not None:
+            sync = self.sync_confidence(kwargs["syncnet"], out_u8, audio_path, video_fps, num_frames)
         frames_out = out_u8
         if video_frames is not None:
             frames_out = self.restore_video(out, video_frames, boxes, affine_matrices)
@@ -638,7 +644,26 @@ class LipsyncPipeline:
                         quality=int(kwargs.get("video_quality", 95)))
             return None
         audio_keep = int(n_out / video_fps * audio_sample_rate)
+        extra = {} if sync is None else dict(sync_scores=sync.numpy(), sync_conf=np.float32(self.last_sync_conf))
         np.savez(video_out_path if video_out_path.endswith(".npz") else video_out_path + ".npz",
                  frames=frames_out.cpu().numpy(), audio=np.asarray(audio_samples[:audio_keep]),
-                 fps=video_fps, sample_rate=audio_sample_rate, padding_duration=padding_duration)
+                 fps=video_fps, sample_rate=audio_sample_rate, padding_duration=padding_duration, **extra)
         return None
+
+    def sync_confidence(self, net, faces_u8, audio_path, video_fps=25, num_frames=16):
+        """StableSyncNet's verdict on a result (syncnet.py; eval/eval_syncnet_acc.py): the synced
+        aligned faces (run_windows' uint8 (n, R, R, 3)) in windows of num_frames against the
+        request's audio at 16 kHz, zero-padded or cut to n / video_fps seconds (the padding the
+        pipeline adds is silence).  Sets last_sync_scores (fp32 CPU tensor, one per window) and
+        last_sync_conf (their mean; nan without a window) and returns the scores."""
+        from . import syncnet as sn
+        from .audio import read_audio
+        n = faces_u8.shape[0]
+        wav = read_audio(audio_path, sn.SAMPLE_RATE).float()
+        want = int(n / video_fps * sn.SAMPLE_RATE)
+        wav = wav[:want] if wav.numel() >= want else torch.cat([wav, torch.zeros(want - wav.numel())])
+        scores, _ = sn.sync_scores(net, faces_u8, wav, fps=video_fps, num_frames=num_frames, stride=num_frames,
+                                   resolution=getattr(net, "resolution", None))
+        self.last_sync_scores = scores.float().cpu()
+        self.last_sync_conf = float(self.last_sync_scores.mean()) if scores.numel() else float("nan")
+        return self.last_sync_scores

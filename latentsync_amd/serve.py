@@ -108,6 +108,11 @@ def run_job(pipeline, payload: dict, data_dir: str, results_dir: str, resolution
     landmarks_path = data_path[:-len(".pth")] + ".landmarks.npy"
     if payload.get("use_darken") and os.path.exists(landmarks_path):
         kw["face_landmarks"] = landmarks_path
+    # a worker started with LATENTSYNC_SYNCNET_CKPT carries a StableSyncNet (default_pipeline):
+    # the result is scored and the reply gains "sync_conf"
+    net = getattr(pipeline, "syncnet", None)
+    if net is not None:
+        kw["syncnet"] = net
     pipeline(video_path=video_path, audio_path=audio_path, video_out_path=video_out_path,
              video_mask_path=os.path.join(results_dir, f"{payload['id']}_mask.npz"), num_frames=16, num_inference_steps=20,
              guidance_scale=1.5, width=resolution, height=resolution, data_path=data_path,
@@ -115,8 +120,11 @@ def run_job(pipeline, payload: dict, data_dir: str, results_dir: str, resolution
              force_video_length=payload.get("force_video_length") or False,
              use_darken=payload.get("use_darken") or False,
              brightness_factor=calculate_inverse_factor(payload.get("brightness_factor") or 1), **kw)
-    return {"message": "Request processed successfully", "output_url": video_out_path, "gif_url": None,
-            "elapsed_time": time.time() - start, "request_uuid": str(uuid.uuid4())}
+    reply = {"message": "Request processed successfully", "output_url": video_out_path, "gif_url": None,
+             "elapsed_time": time.time() - start, "request_uuid": str(uuid.uuid4())}
+    if net is not None:
+        reply["sync_conf"] = float(pipeline.last_sync_conf)
+    return reply
 
 
 # --------------------------------------------------------------------------
@@ -406,7 +414,14 @@ def default_pipeline(rank):
     audio = Audio2Feature(model_path=os.environ.get("LATENTSYNC_WHISPER", "checkpoints/whisper/tiny.pt"), device=dev,
                           num_frames=cfg["data"]["num_frames"])
     sched = DDIMScheduler.from_pretrained("configs")
-    return LipsyncPipeline(vae=vae, audio_encoder=audio, denoising_unet=unet, scheduler=sched).to(dev)
+    pipe = LipsyncPipeline(vae=vae, audio_encoder=audio, denoising_unet=unet, scheduler=sched).to(dev)
+    if os.environ.get("LATENTSYNC_SYNCNET_CKPT"):
+        # opt-in sync confidence: run_job passes pipe.syncnet on and reports last_sync_conf
+        from .syncnet import StableSyncNet
+        scfg = load_config(os.environ.get("LATENTSYNC_SYNCNET_CONFIG", "configs/syncnet/syncnet_16_pixel_attn.yaml"))
+        pipe.syncnet = StableSyncNet.from_pretrained(scfg["model"], os.environ["LATENTSYNC_SYNCNET_CKPT"], device=dev)
+        pipe.syncnet.resolution = (scfg.get("data") or {}).get("resolution")
+    return pipe
 
 
 def main():
