@@ -780,6 +780,70 @@ int ls_conv3x3_strided(const uint16_t* x, int32_t ldx, int32_t n_img, int32_t H,
 int ls_sync_score(const uint16_t* v_in, int32_t ldv, const uint16_t* a_in, int32_t lda, int32_t B, int32_t D,
                   float* v, float* a, int32_t ldo, float* score, void* stream);
 
+/* ---- GIF thumbnail of a result, thumbnail.py of the reference (additive, ABI stays 14) -- */
+
+/* cv2.resize(frame, (dw, dh), interpolation=INTER_AREA) for n uint8 RGB frames
+ * [n][H][W][3] -> [n][dh][dw][3], downscale only (dh <= H, dw <= W).  As OpenCV defines it:
+ * per axis scale = 1 / (dst / src) in fp64; destination index d covers the source cell
+ * [d scale, (d + 1) scale) and takes the source samples it touches, a partial one weighted
+ * by its covered fraction over the cell width (computeResizeAreaTab, weights cast to
+ * fp32).  fp32 sums, the columns of one source row first (from 0), the rows second, one
+ * rounding per multiply and per add, then saturate_cast<uchar> (round half to even).  When
+ * both scales are integers: the integer sum of the cell times the fp32 1 / area, rounded
+ * the same way ((sum + 2) >> 2 for 2 x 2).  One launch, no workspace, no synchronisation.
+ * LS_ERR_INVALID, nothing launched: null pointers, n < 1, a size outside 1..65535, an
+ * upscale on either axis. */
+int ls_resize_area_u8(const uint8_t* src, int32_t n, int32_t H, int32_t W, uint8_t* dst, int32_t dh, int32_t dw,
+                      void* stream);
+
+/* Blends up to 16 layers into n uint8 RGB frames [n][H][W][3] in place, the same layers
+ * into every frame.  `layers` is a HOST array int32 [n_layers][8] = {x0, y0, w, h, offset,
+ * r, g, b} (it travels as a kernel argument): the layer covers the frame box [x0, x0 + w)
+ * x [y0, y0 + h) (clipped to the frame; w or h 0: an empty layer) with the row-major uint8
+ * alpha map alpha[offset .. offset + w h) on the device and the ink (r, g, b).  Every
+ * pixel walks its layers in order with Pillow's blend, per channel
+ *   t = ink a + dst (255 - a) + 128;  dst = ((t >> 8) + t) >> 8.
+ * One launch (none when no layer has pixels).  LS_ERR_INVALID, nothing launched: null
+ * frames, n, H or W < 1, n_layers outside 0..16, a negative w, h or offset, a map that
+ * passes alpha_bytes, an ink outside 0..255, null layers / alpha where they are needed. */
+int ls_overlay_blend_u8(uint8_t* frames, int32_t n, int32_t H, int32_t W, const int32_t* layers, int32_t n_layers,
+                        const uint8_t* alpha, int64_t alpha_bytes, void* stream);
+
+/* hist uint32 [32768]: the number of pixels of the n uint8 RGB frames [n][H][W][3] in each
+ * 5-5-5 bin (r >> 3) << 10 | (g >> 3) << 5 | b >> 3.  The call zeroes hist first (a memset
+ * on the stream); counts are exact.  LS_ERR_INVALID: null pointers, n, H or W < 1, more
+ * than 2^32 - 1 pixels. */
+int ls_rgb555_hist(const uint8_t* frames, int32_t n, int32_t H, int32_t W, uint32_t* hist, void* stream);
+
+/* idx uint8 [n][H][W] = lut[5-5-5 bin of the pixel], lut uint8 [32768] on the device.
+ * LS_ERR_INVALID: null pointers, n, H or W < 1. */
+int ls_palette_map(const uint8_t* frames, int32_t n, int32_t H, int32_t W, const uint8_t* lut, uint8_t* idx,
+                   void* stream);
+
+/* GIF LZW (minimum code size 8: CLEAR 256, EOI 257, first code 258) of n index frames
+ * uint8 [n][H][W]: the raw code bytes of every frame (before the split into 255-byte
+ * sub-blocks, which the host does), LSB first, each frame padded to a whole byte.
+ * A frame is cut into strips of ls_gif_strip_rows() rows (the last may be shorter), coded
+ * independently and concatenated bit by bit into one ordinary stream: the first strip
+ * starts with CLEAR; every strip starts from an empty dictionary at width 9; the width
+ * grows when the decoder's next free code reaches 1 << width (no early change); once code
+ * 4095 has been assigned the strip emits CLEAR (at width 12) and starts over; a strip ends
+ * with its last code, then CLEAR -- EOI for the last strip of the frame -- at the width a
+ * decoder has after that last code.
+ *   out      uint8 [out_capacity]: frame after frame
+ *   offsets  int64 [n + 1]: frame f occupies out[offsets[f] .. offsets[f + 1])
+ * Bytes that would land at or past out_capacity are dropped while the offsets stay exact,
+ * so offsets[n] > out_capacity tells the caller to retry with a larger buffer.  The
+ * workspace (ls_gif_lzw_workspace_bytes; about 1.5 bytes per pixel) holds every strip's
+ * worst case, (pixels + 2) codes of 12 bits, so no content can overflow it.  No
+ * allocation, no synchronisation.  LS_ERR_INVALID, nothing launched: null pointers, n, H
+ * or W outside 1..65535, negative out_capacity (ls_gif_lzw_workspace_bytes returns 0 for
+ * such sizes); LS_ERR_WORKSPACE: workspace null or too small. */
+int ls_gif_strip_rows(void);
+size_t ls_gif_lzw_workspace_bytes(int32_t n, int32_t H, int32_t W);
+int ls_gif_lzw(const uint8_t* idx, int32_t n, int32_t H, int32_t W, uint8_t* out, int64_t out_capacity,
+               int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream);
+
 int ls_abi_version(void);
 const char* ls_last_error(void);
 

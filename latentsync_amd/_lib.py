@@ -158,6 +158,14 @@ _SIGS = {
                                      C.c_int32, c_vp, C.c_int32, c_vp]),
     "ls_sync_score": (C.c_int, [c_vp, C.c_int32, c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, c_vp, C.c_int32, c_vp,
                                 c_vp]),
+    "ls_resize_area_u8": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, C.c_int32, C.c_int32, c_vp]),
+    "ls_overlay_blend_u8": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, c_vp,
+                                      C.c_int64, c_vp]),
+    "ls_rgb555_hist": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, c_vp]),
+    "ls_palette_map": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, c_vp, c_vp]),
+    "ls_gif_strip_rows": (C.c_int, []),
+    "ls_gif_lzw_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "ls_gif_lzw": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, C.c_int64, c_vp, c_vp, C.c_size_t, c_vp]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -828,3 +828,119 @@ def add_rows(x2d, table, out=None):
     check(lib.ls_add_rows(_p(x2d), rows, C_, x2d.stride(0), _p(table), table.shape[0], _p(out), out.stride(0),
                           _stream()), "ls_add_rows")
     return out
+
+
+# ---- GIF thumbnail (thumbnail.py; csrc/ls_thumb.hip) ----------------------------------
+
+
+def _rgb_frames(frames_u8, what):
+    if (not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or
+            frames_u8.shape[-1] != 3 or not frames_u8.is_cuda):
+        raise ValueError(f"{what}: uint8 (n, H, W, 3) on the device expected, got "
+                         f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
+    if not frames_u8.is_contiguous():
+        raise ValueError(f"{what}: frames must be contiguous")
+    return frames_u8.shape[:3]
+
+
+def resize_area_u8(frames_u8, out_h, out_w):
+    """cv2.resize(frame, (out_w, out_h), interpolation=INTER_AREA) of uint8 RGB frames
+    (n, H, W, 3) on the device -> (n, out_h, out_w, 3) (ls_resize_area_u8; downscale only)."""
+    lib = _lib.load()
+    n, H, W = _rgb_frames(frames_u8, "resize_area_u8")
+    out_h, out_w = int(out_h), int(out_w)
+    out = torch.empty((n, out_h, out_w, 3), dtype=torch.uint8, device=frames_u8.device)
+    if n:
+        with torch.cuda.device(frames_u8.device):
+            check(lib.ls_resize_area_u8(_p(frames_u8), n, H, W, _p(out), out_h, out_w, _stream()), "ls_resize_area_u8")
+    return out
+
+
+def overlay_blend_u8(frames_u8, layers):
+    """Blends ``layers`` -- a sequence of (x0, y0, alpha uint8 (h, w) array, (r, g, b)), at
+    most 16, applied in order -- into uint8 RGB frames (n, H, W, 3) on the device, in place
+    (ls_overlay_blend_u8: Pillow's blend per channel).  Returns the frames."""
+    import numpy as np
+    lib = _lib.load()
+    n, H, W = _rgb_frames(frames_u8, "overlay_blend_u8")
+    layers = list(layers)
+    desc, maps, off = [], [], 0
+    for x0, y0, a, ink in layers:
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.ndim != 2:
+            raise ValueError(f"overlay_blend_u8: an alpha map must be 2-D, got shape {a.shape}")
+        desc.append([int(x0), int(y0), a.shape[1], a.shape[0], off, int(ink[0]), int(ink[1]), int(ink[2])])
+        maps.append(a.reshape(-1))
+        off += a.size
+    if n == 0:
+        return frames_u8
+    alpha = None
+    if off:
+        alpha = torch.from_numpy(np.concatenate(maps)).to(frames_u8.device)
+    d = (C.c_int32 * (8 * len(desc)))(*[v for row in desc for v in row]) if desc else None
+    with torch.cuda.device(frames_u8.device):
+        check(lib.ls_overlay_blend_u8(_p(frames_u8), n, H, W, d, len(desc), _p(alpha), off, _stream()),
+              "ls_overlay_blend_u8")
+    return frames_u8
+
+
+def rgb555_hist(frames_u8):
+    """uint8 RGB frames (n, H, W, 3) on the device -> int64 (32768,) on the device: the pixel
+    count of every 5-5-5 bin r >> 3 << 10 | g >> 3 << 5 | b >> 3 (ls_rgb555_hist; the kernel
+    counts in uint32)."""
+    lib = _lib.load()
+    n, H, W = _rgb_frames(frames_u8, "rgb555_hist")
+    hist = torch.zeros(32768, dtype=torch.int32, device=frames_u8.device)
+    if n:
+        with torch.cuda.device(frames_u8.device):
+            check(lib.ls_rgb555_hist(_p(frames_u8), n, H, W, _p(hist), _stream()), "ls_rgb555_hist")
+    return hist.to(torch.int64) & 0xffffffff
+
+
+def palette_map(frames_u8, lut):
+    """uint8 RGB frames (n, H, W, 3) -> uint8 (n, H, W): lut[5-5-5 bin] per pixel, with lut a
+    uint8 (32768,) tensor on the frames' device (ls_palette_map)."""
+    lib = _lib.load()
+    n, H, W = _rgb_frames(frames_u8, "palette_map")
+    if (not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or tuple(lut.shape) != (32768,) or
+            lut.device != frames_u8.device or not lut.is_contiguous()):
+        raise ValueError("palette_map: lut must be a contiguous uint8 (32768,) tensor on the frames' device")
+    idx = torch.empty((n, H, W), dtype=torch.uint8, device=frames_u8.device)
+    if n:
+        with torch.cuda.device(frames_u8.device):
+            check(lib.ls_palette_map(_p(frames_u8), n, H, W, _p(lut), _p(idx), _stream()), "ls_palette_map")
+    return idx
+
+
+def gif_lzw(idx_u8, workspace=None, capacity=None):
+    """GIF LZW code bytes (minimum code size 8) of uint8 index frames (n, H, W) on the device
+    (ls_gif_lzw) -> (bytes uint8 (total,), offsets int64 (n + 1,)), both on the device; frame
+    f's codes are bytes[offsets[f]:offsets[f + 1]], not yet split into sub-blocks.  The output
+    buffer starts at ``capacity`` bytes (default: the raw size) and the call is repeated once
+    with the exact size when the codes are larger.  There is no CPU path."""
+    lib = _lib.load()
+    if (not isinstance(idx_u8, torch.Tensor) or idx_u8.dtype != torch.uint8 or idx_u8.dim() != 3 or
+            not idx_u8.is_cuda or not idx_u8.is_contiguous()):
+        raise ValueError("gif_lzw: contiguous uint8 (n, H, W) on the device expected, got "
+                         f"{getattr(idx_u8, 'dtype', type(idx_u8))} {tuple(getattr(idx_u8, 'shape', ()))}")
+    n, H, W = idx_u8.shape
+    device = idx_u8.device
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    if n == 0:
+        return torch.empty(0, dtype=torch.uint8, device=device), offsets
+    with torch.cuda.device(device):
+        need = lib.ls_gif_lzw_workspace_bytes(n, H, W)
+        if workspace is None:
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+        elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != device:
+            raise ValueError("gif_lzw: workspace must be a contiguous uint8 tensor on the frames' device")
+        capacity = n * H * W + 64 if capacity is None else int(capacity)
+        for _ in range(2):
+            out = torch.empty(max(capacity, 1), dtype=torch.uint8, device=device)
+            check(lib.ls_gif_lzw(_p(idx_u8), n, H, W, _p(out), capacity, _p(offsets), _p(workspace),
+                                 workspace.numel(), _stream()), "ls_gif_lzw")
+            total = int(offsets[-1].item())
+            if total <= capacity:
+                return out[:total], offsets
+            capacity = total
+    raise RuntimeError("gif_lzw: the coded size changed between two runs on the same frames")

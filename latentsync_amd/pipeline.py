@@ -530,7 +530,10 @@ class LipsyncPipeline:
         lip-synced aligned faces are written instead and no warp-back happens.
         ``syncnet=`` (a syncnet.StableSyncNet on this device) scores the synced faces against
         the audio after the window loop (sync_confidence): last_sync_scores / last_sync_conf are
-        set and an .npz output gains ``sync_scores`` and ``sync_conf``; an .avi is unchanged."""
+        set and an .npz output gains ``sync_scores`` and ``sync_conf``; an .avi is unchanged.
+        ``thumbnail_path=`` writes the reference's GIF thumbnail (thumbnail.py) of the frames the
+        writer writes, made on the device just before them, with ``thumbnail_text`` as its
+        subtitle, ``thumbnail_duration`` (6) and ``thumbnail_fps`` (3) as api.py:168-174 sets."""
         from . import repeat as rep
         # write_video's brightness restore runs only `if use_darken and brightness_factor`
         # (util.py:150-151, reached from :594).  It runs on the device (darken.py) from the
@@ -639,16 +642,29 @@ class LipsyncPipeline:
             if keep_f < 1:
                 raise ValueError(f"nothing to write: {n_out} frames at {video_fps} frames/s are all padding "
                                  f"({padding_duration} s)")
+            self._thumbnail(frames_out[:keep_f], video_fps, kwargs)
             write_video(video_out_path, frames_out[:keep_f].contiguous(), video_fps,
                         np.asarray(audio_samples[:keep_a]), audio_sample_rate,
                         quality=int(kwargs.get("video_quality", 95)))
             return None
+        self._thumbnail(frames_out, video_fps, kwargs)
         audio_keep = int(n_out / video_fps * audio_sample_rate)
         extra = {} if sync is None else dict(sync_scores=sync.numpy(), sync_conf=np.float32(self.last_sync_conf))
         np.savez(video_out_path if video_out_path.endswith(".npz") else video_out_path + ".npz",
                  frames=frames_out.cpu().numpy(), audio=np.asarray(audio_samples[:audio_keep]),
                  fps=video_fps, sample_rate=audio_sample_rate, padding_duration=padding_duration, **extra)
         return None
+
+    @staticmethod
+    def _thumbnail(frames_u8, video_fps, kwargs):
+        """The GIF thumbnail of the frames about to be written, when thumbnail_path= asks for one."""
+        if not kwargs.get("thumbnail_path"):
+            return
+        from .thumbnail import create_video_thumbnail_gif
+        text = {} if kwargs.get("thumbnail_text") is None else dict(subtitle_text=kwargs["thumbnail_text"])
+        create_video_thumbnail_gif(frames_u8.contiguous(), video_fps, kwargs["thumbnail_path"],
+                                   duration=kwargs.get("thumbnail_duration", 6), fps=kwargs.get("thumbnail_fps", 3),
+                                   **text)
 
     def sync_confidence(self, net, faces_u8, audio_path, video_fps=25, num_frames=16):
         """StableSyncNet's verdict on a result (syncnet.py; eval/eval_syncnet_acc.py): the synced

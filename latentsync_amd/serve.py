@@ -17,10 +17,12 @@ MI355X-first dispatch: instead of one pipeline behind asyncio.Semaphore(1)
 each bound to its device before it touches HIP) and a consumer per worker takes the
 next queued request as soon as its GPU is free -- up to N requests in flight on an
 N-GPU node, each worker still strictly one request at a time (the pipeline is not
-re-entrant).  Out of scope (no network): the GCS upload and the
-GIF thumbnail (api.py:156-179) -- `output_url` is the local result path and
-`gif_url` is None -- and downloading `audio_url` (a local path or file:// URL is
-copied into place).
+re-entrant).  A dynamic-clip request with a text gets the reference's GIF thumbnail
+(api.py:164-174; thumbnail.py, made on the device from the frames the writer writes):
+`gif_url` is its local path, None for every other request.  Out of scope (no network,
+SURVEY.md §8(f)): the GCS upload (api.py:156-179) -- `output_url` and `gif_url` are
+local paths -- and downloading `audio_url` (a local path or file:// URL is copied
+into place).
 """
 import asyncio
 import multiprocessing as mp
@@ -113,6 +115,14 @@ def run_job(pipeline, payload: dict, data_dir: str, results_dir: str, resolution
     net = getattr(pipeline, "syncnet", None)
     if net is not None:
         kw["syncnet"] = net
+    # api.py:164-174: a dynamic clip with a text gets a GIF thumbnail (duration 6, fps 3, the
+    # pipeline's defaults) with the text as its subtitle
+    gif_path = None
+    if payload.get("is_dynamic_clip") and payload.get("text"):
+        gif_path = os.path.join(results_dir, f"{payload['id']}.gif")
+        if os.path.exists(gif_path):
+            os.remove(gif_path)  # an earlier request's file must not answer for this one
+        kw["thumbnail_path"], kw["thumbnail_text"] = gif_path, payload["text"]
     pipeline(video_path=video_path, audio_path=audio_path, video_out_path=video_out_path,
              video_mask_path=os.path.join(results_dir, f"{payload['id']}_mask.npz"), num_frames=16, num_inference_steps=20,
              guidance_scale=1.5, width=resolution, height=resolution, data_path=data_path,
@@ -120,7 +130,8 @@ def run_job(pipeline, payload: dict, data_dir: str, results_dir: str, resolution
              force_video_length=payload.get("force_video_length") or False,
              use_darken=payload.get("use_darken") or False,
              brightness_factor=calculate_inverse_factor(payload.get("brightness_factor") or 1), **kw)
-    reply = {"message": "Request processed successfully", "output_url": video_out_path, "gif_url": None,
+    reply = {"message": "Request processed successfully", "output_url": video_out_path,
+             "gif_url": gif_path if gif_path is not None and os.path.exists(gif_path) else None,
              "elapsed_time": time.time() - start, "request_uuid": str(uuid.uuid4())}
     if net is not None:
         reply["sync_conf"] = float(pipeline.last_sync_conf)
