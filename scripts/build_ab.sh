@@ -1,12 +1,14 @@
 #!/bin/bash
-# Build an A/B variant of libls_hip.so: the current sources with ONE file taken from
+# Build an A/B variant of libls_hip.so: the current sources with some files taken from
 # another commit, written to latentsync_amd/libls_hip_ab.so (select it at run time
 # with LS_HIP_LIB=latentsync_amd/libls_hip_ab.so).
-# usage: bash scripts/build_ab.sh COMMIT [csrc file(s), default ls_gemm.hip]
+# usage: bash scripts/build_ab.sh COMMIT [csrc file(s), default: the conv / GEMM sources and headers]
+#        (a COMMIT from before the split into ls_conv*.hip has none of them: name its files)
 #        COMMIT "-" = the working tree's file; EXTRA_FLAGS (env) adds hipcc flags (-DMACRO=...);
 #        AB_OUT (env) names the output library (default latentsync_amd/libls_hip_ab.so)
 set -e
-commit=$1; shift; files=${*:-ls_gemm.hip}
+commit=$1; shift
+files=${*:-ls_conv.h ls_conv_tiled.h ls_conv.hip ls_conv_tiled.hip ls_conv_big.hip ls_conv_rowblock.hip ls_conv_halo.hip}
 root=$(cd "$(dirname "$0")/.." && pwd)
 out=${AB_OUT:-latentsync_amd/libls_hip_ab.so}
 ab=$root/build/ab

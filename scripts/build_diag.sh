@@ -1,6 +1,7 @@
 #!/bin/bash
 # Diagnostic variant of libls_hip.so: the current sources with -D$1 (an ablation switch,
-# e.g. LS_TATTN_ABLATE or LS_GEMM_ABLATE), written to latentsync_amd/libls_hip_ab.so --
+# e.g. LS_TATTN_ABLATE (ls_motion.hip; scripts/tattn_ablate.sh) or LS_GEMM_ABLATE
+# (conv_gemm_dma_kernel, ls_conv_tiled.hip)), written to latentsync_amd/libls_hip_ab.so --
 # select it at run time with LS_HIP_LIB=latentsync_amd/libls_hip_ab.so.
 # usage: bash scripts/build_diag.sh DEFINE
 set -e

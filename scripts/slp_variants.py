@@ -1,8 +1,8 @@
 """Build the A/B libraries of the gfx950 SLP investigation:
 
-  slp     ls_gemm.hip with SLP vectorisation on (the build that produced wrong
-          LayerNorm-folded row-block rows), everything else as shipped;
-  slp_bw  slp + every hand-written `s_waitcnt vmcnt(N)` of ls_gemm.hip replaced by
+  slp     the conv / GEMM sources (ls_conv*.hip) with SLP vectorisation on (the build that
+          produced wrong LayerNorm-folded row-block rows), everything else as shipped;
+  slp_bw  slp + every hand-written `s_waitcnt vmcnt(N)` (wait_vm, ls_common.h) replaced by
           __builtin_amdgcn_s_waitcnt (an S_WAITCNT the compiler's own waitcnt pass
           sees), i.e. no inline asm the compiler cannot reason about;
   slp_noasm  slp_bw + the row-block kernel's remaining inline asm (lgkmcnt waits and
@@ -35,20 +35,30 @@ WAIT_BUILTIN = ("template <int N> __device__ __forceinline__ void wait_vm() "
 LN_END = "  wait_vm<0>();\n  __builtin_amdgcn_s_barrier();\n  asm volatile(\"\" ::: \"memory\");\n\n  f32x4 acc0[FM][FN]"
 
 
-def variant(name, src, extra=()):
+# the conv / GEMM translation units (the variants build all five with SLP on); the patched
+# inline asm is the row-block kernel's, the wait_vm template is ls_common.h's
+CONV = ("ls_conv.hip", "ls_conv_tiled.hip", "ls_conv_big.hip", "ls_conv_rowblock.hip", "ls_conv_halo.hip")
+RB = "ls_conv_rowblock.hip"
+
+
+def variant(name, edits=(), extra=()):
+    """edits: (file, old, new), each `old` exactly once in csrc/file."""
     top = os.path.join(OUT, name)
     shutil.rmtree(top, ignore_errors=True)
     d = os.path.join(top, "pkg", "csrc")  # csrc/../../include/ls_hip.h resolves as in-tree
     shutil.copytree(CSRC, d)
     shutil.copytree(os.path.join(ROOT, "include"), os.path.join(top, "include"))
-    with open(os.path.join(d, "ls_gemm.hip"), "w") as f:
-        f.write(src)
+    for fn, old, new in edits:
+        src = open(os.path.join(d, fn)).read()
+        assert src.count(old) == 1, (fn, old)
+        with open(os.path.join(d, fn), "w") as f:
+            f.write(src.replace(old, new))
     objs = []
     procs = []
     for fn in sorted(os.listdir(d)):
         if not fn.endswith(".hip"):
             continue
-        flags = FLAGS + (list(extra) if fn == "ls_gemm.hip" else ["-fno-slp-vectorize"])
+        flags = FLAGS + (list(extra) if fn in CONV else ["-fno-slp-vectorize"])
         o = os.path.join(d, fn[:-4] + ".o")
         procs.append(subprocess.Popen([HIPCC] + flags + ["-c", os.path.join(d, fn), "-o", o]))
         objs.append(o)
@@ -58,7 +68,7 @@ def variant(name, src, extra=()):
     subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
     # device disassembly of the LN-folded row-block kernel (FLAGS = RB_LN)
     s = subprocess.run([HIPCC] + FLAGS + list(extra) + ["--cuda-device-only", "-S",
-                        os.path.join(d, "ls_gemm.hip"), "-o", "-"], capture_output=True, text=True).stdout
+                        os.path.join(d, RB), "-o", "-"], capture_output=True, text=True).stdout
     sym = "_ZN2ls20gemm_rowblock_kernelILi10ELi2ELi2ELi1EEEvNS_8ConvArgsE:"
     body = s[s.index(sym):]
     body = body[:body.index(".Lfunc_end", 1)]
@@ -72,25 +82,23 @@ def main():
     if only:
         global variant
         build = variant
-        variant = lambda name, src, extra=(): build(name, src, extra) if name in only else None
-    base = open(os.path.join(CSRC, "ls_gemm.hip")).read()
-    assert WAIT_ASM in base and base.count(LN_END) == 1
+        variant = lambda name, edits=(), extra=(): build(name, edits, extra) if name in only else None
     os.makedirs(OUT, exist_ok=True)
-    variant("slp", base)
-    variant("slp_bw", base.replace(WAIT_ASM, WAIT_BUILTIN))
+    builtin_wait = ("ls_common.h", WAIT_ASM, WAIT_BUILTIN)
+    variant("slp")
+    variant("slp_bw", [builtin_wait])
     rb_sync = ('    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");\n    __builtin_amdgcn_s_barrier();\n'
                '    asm volatile("" ::: "memory");\n  };')
     ln_sync = '  __builtin_amdgcn_s_barrier();\n  asm volatile("" ::: "memory");\n\n  f32x4 acc0[FM][FN]'
-    assert base.count(rb_sync) == 1 and base.count(ln_sync) == 1
-    noasm = base.replace(WAIT_ASM, WAIT_BUILTIN).replace(rb_sync, "    __syncthreads();\n  };")
-    variant("slp_noasm", noasm.replace(ln_sync, "  __syncthreads();\n\n  f32x4 acc0[FM][FN]"))
+    variant("slp_noasm", [builtin_wait, (RB, rb_sync, "    __syncthreads();\n  };"),
+                          (RB, ln_sync, "  __syncthreads();\n\n  f32x4 acc0[FM][FN]")])
     # compiler-side knobs on the unchanged source: 4 wait states before every
     # instruction (a VALU / MFMA hazard that needs more nops than the compiler
     # inserts disappears), and every s_waitcnt forced to zero (a memory-counter race
     # disappears)
-    variant("slp_nop", base, ["-mllvm", "-amdgpu-snop-padding=4"])
-    variant("slp_wz", base, ["-mllvm", "-amdgpu-waitcnt-forcezero"])
-    variant("slp_sb", base.replace(LN_END, LN_END.replace("  wait_vm<0>();\n", "  __builtin_amdgcn_sched_barrier(0);\n  wait_vm<0>();\n", 1)))
+    variant("slp_nop", extra=["-mllvm", "-amdgpu-snop-padding=4"])
+    variant("slp_wz", extra=["-mllvm", "-amdgpu-waitcnt-forcezero"])
+    variant("slp_sb", [(RB, LN_END, LN_END.replace("  wait_vm<0>();\n", "  __builtin_amdgcn_sched_barrier(0);\n  wait_vm<0>();\n", 1))])
 
 
 if __name__ == "__main__":

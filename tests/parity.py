@@ -334,7 +334,7 @@ def gn_colsum_bound(cs, slots_per_sample, groups, eps, gamma, beta, slot_rows=12
 
 
 def colsum_bound(y, slot_rows=128):
-    """(ref, B), each (M / 128, 2, N), for ls_gn_colsum (colsum_pass_kernel, ls_gemm.hip): per
+    """(ref, B), each (M / 128, 2, N), for ls_gn_colsum (colsum_pass_kernel, ls_conv.hip): per
     128-row slot the column sums of y and of y^2.  y is bf16, so y^2 is exact in fp32 (and the
     kernel's fma adds it unrounded); what rounds is the additions: 8 chains of 16 rows and the
     8-way merge, fewer than 128 in all, any order: B = 128 2^-23 sum |terms|."""

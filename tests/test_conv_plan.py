@@ -23,7 +23,7 @@ NB = 768  # images per UNet call at the bench configuration
 ROWS32, ROWS16, ROWS8, ROWS4 = NB * 1024, NB * 256, NB * 64, NB * 16
 # tuning keys the corpus touches, with their defaults (restored after every row)
 WS = 256 << 20  # the split-K workspace ops.conv hands ls_conv2d
-DEFAULTS = {1: 0, 2: 0, 3: 0, 6: 1, 8: 1, 15: 1, 16: 1, 18: 1, 19: 1}
+DEFAULTS = {1: 0, 2: 0, 3: 0, 6: 1, 7: 1, 8: 1, 13: 0, 15: 1, 16: 1, 18: 1, 19: 1, 20: 0}
 
 
 def _row(name, kind, x, w, tune=None, **call):
@@ -174,6 +174,10 @@ CORPUS = [
     # not the row-block kernel's (ops.conv_path asks without one and hears 1)
     _lin("rb640_few_rows_workspace_splits", "edge", 256, 640, 192, workspace_bytes=WS),
     _lin("rb640_few_rows", "edge", 256, 640, 192),
+    # ---- the keys read outside the planner's own file: 7 and 20 by the row-block GEMM's, 13 by the halo conv's
+    _lin("rb640_key7_off", "edge", 256, 640, 640, tune={7: 0}),
+    _lin("rb640_res_key20", "edge", 256, 640, 640, tune={20: 1}, res=True),
+    _row("halo_bn128_key13", "edge", (2, 16, 16, 64), (640, 3), tune={13: 1}),
 ]
 
 # rows where 41d7641's ls_conv_path named another family than its ls_conv2d launched
@@ -256,7 +260,7 @@ def _ask(row, what):
         x, pw, kw = _args(call)
         return what(x, pw, **kw)
     finally:
-        for k, v in {**DEFAULTS, 20: 0}.items():
+        for k, v in DEFAULTS.items():
             assert lib.ls_set_tuning(k, v) == 0
 
 
@@ -513,4 +517,9 @@ PINS = {
     "split_key3": "0: tile 128x128 ks1 tapu0 buf1 epi2 split2 | 192x256 lds65536 | +reduce | ws12582912",
     "rb640_few_rows_workspace_splits": "0: tile 64x64 ks1 tapu0 buf1 epi2 split2 | 24x256 lds32768 | +reduce | ws393216",
     "rb640_few_rows": "1: rowblock kt20 fm2 flags0 split1 | 6x512 lds125184 | - | ws0",
+    # (these three, and their conv_path_parent.json entries, as commit 82f8434 answered: with the key at its
+    # default the plans are rowblock kt20 fm2 flags0, tile 64x64 and halo bn160 th16)
+    "rb640_key7_off": "0: tile 64x64 ks1 tapu0 buf1 epi0 split1 | 40x256 lds32768 | - | ws0",
+    "rb640_res_key20": "1: rowblock kt20 fm2 flags2 split1 | 20x512 lds174336 | - | ws0",
+    "halo_bn128_key13": "3: halo bn128 th8 gn0 cs0 ph0 split1 | 20x256 lds80896 | - | ws0",
 }

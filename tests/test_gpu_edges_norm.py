@@ -1,4 +1,4 @@
-"""ls_norm.hip (and ls_gn_colsum of ls_gemm.hip) per element: every entry point is called through
+"""ls_norm.hip (and ls_gn_colsum of ls_conv.hip) per element: every entry point is called through
 the C ABI so that its outputs sit in sentinel guard bands (bf16 outputs in the bf16 NaN, scale /
 shift / statistics in the fp32 NaN), its activation inputs sit in guarded buffers too -- NaN rows
 behind the last valid row and NaNs in every pitch gap, so a read past the input shows up in the
