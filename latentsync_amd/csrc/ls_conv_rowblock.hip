@@ -393,7 +393,9 @@ bool rowblock_ok(const ls_conv_desc* d, const ConvArgs& a) {
   return (((uintptr_t)a.x1 | (uintptr_t)a.bias | (uintptr_t)a.ln_cs | (uintptr_t)a.rowvec) & 15) == 0;
 }
 
-// the compiled FLAGS combinations, each at <KT 10, FM 2>, <20, 1> and, without RB_FM1, <20, 2>
+// the compiled FLAGS combinations, each at <KT 10, FM 2>, <20, 1> and, without RB_FM1_K640, <20, 2>.
+// Every flag set added here needs its per-element cases in tests/test_gpu_edges_conv_fused.py
+// (RB_FLAG_SETS there; test_every_rowblock_instance_ran counts the instances the plans reported)
 using RowblockInstances =
     std::integer_sequence<int, 0, RB_LN, RB_LN | RB_RV, RB_RES, RB_LN | RB_RES, RB_LN | RB_GEGLU, RB_GEGLU, RB_STATS,
                           RB_RES | RB_STATS, RB_RES | RB_GNCS, RB_AFF, RB_AFF | RB_STATS>;
@@ -401,6 +403,12 @@ using RowblockInstances =
 // affine a block looks its sample up once (rowblock_ok only guarantees pix_per_sample % 128
 // == 0 at K = 640)
 constexpr int RB_FM1 = RB_STATS | RB_GNCS | RB_AFF;
+// ... and at K = 640 also with a residual (tuning key 20): three stages of 40 KB of W images and a
+// 256-row residual tile of 16 KB are 170 KB, more LDS than a workgroup can have.  <20, 2> was
+// planned for it under tuning key 15 and every such launch refused ("invalid argument");
+// tests/test_gpu_edges_conv_fused.py found it.
+constexpr int RB_FM1_K640 = RB_FM1 | RB_RES;
+constexpr size_t RB_LDS_MAX = 160 << 10;  // LDS of a gfx950 workgroup
 
 // FN = 2 (32-column chunks): the FN = 4 variant needs > 256 VGPRs and spills, and a
 // spill's scratch traffic would break the kernel's counted vmcnt waits.
@@ -421,7 +429,7 @@ bool plan_rowblock(ConvPlan& p) {
   const int flags = (a.ln_mr ? RB_LN : 0) | (a.res ? RB_RES : 0) | (a.rowvec ? RB_RV : 0) |
                     (a.act == LS_ACT_GEGLU ? RB_GEGLU : 0) | (a.stats_out ? RB_STATS : 0) | (a.cs_out ? RB_GNCS : 0) |
                     (a.aff_scale ? RB_AFF : 0);
-  const int fm = a.K == 320 || (g_tune.rb640_fm2 && !(flags & RB_FM1)) ? 2 : 1, bm = 128 * fm;
+  const int fm = a.K == 320 || (g_tune.rb640_fm2 && !(flags & RB_FM1_K640)) ? 2 : 1, bm = 128 * fm;
   if (a.M % bm || !rowblock_compiled(flags, RowblockInstances{})) return false;
   const int ntm = a.M / bm, nch = a.N / 32;
   const int ntn = std::max(1, std::min(nch, (256 + ntm - 1) / ntm));
@@ -440,8 +448,10 @@ bool plan_rowblock(ConvPlan& p) {
 
 template <int FLAGS>
 static void launch_rowblock1(const ConvPlan& p, hipStream_t s) {
+  static_assert(rowblock_lds(10, 2, FLAGS) <= RB_LDS_MAX && rowblock_lds(20, 1, FLAGS) <= RB_LDS_MAX, "row-block LDS");
   if (p.i.rb_kt == 10) return launch_plan<gemm_rowblock_kernel<10, 2, 2, FLAGS>>(p, s);
-  if constexpr (!(FLAGS & RB_FM1)) {
+  if constexpr (!(FLAGS & RB_FM1_K640)) {
+    static_assert(rowblock_lds(20, 2, FLAGS) <= RB_LDS_MAX, "row-block LDS");
     if (p.i.rb_fm == 2) return launch_plan<gemm_rowblock_kernel<20, 2, 2, FLAGS>>(p, s);
   }
   launch_plan<gemm_rowblock_kernel<20, 1, 2, FLAGS>>(p, s);

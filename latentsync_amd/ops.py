@@ -101,7 +101,8 @@ def conv(x, pw: Packed, *, x2=None, aff=None, stride=1, pad=None, upsample=False
     upsample = nearest x2 before the 3x3: with pw.phase set, as four 2x2 phase convs
     (ls_conv_desc.upsample = 2) where ls_conv_path takes that form (4, 5), else the 9-tap form;
     gn_out = also emit the output's GroupNorm column sums (ls_conv_desc.gn_colsum_out),
-    attached to the result as `.gn_cs` for group_norm() (when rows % 128 == 0);
+    attached to the result as `.gn_cs` for group_norm() (when rows % 128 == 0); a caller's
+    contiguous fp32 (rows / 128, 2, n_out) tensor instead of True receives them (shape-checked);
     aff_materialize = when the call would take the register-staged GEMM for the affine
     prologue (ls_conv_path 2), apply it with ls_groupnorm_apply first instead (the
     row-block GEMM folds it into its register-resident A rows);
@@ -165,9 +166,16 @@ def conv(x, pw: Packed, *, x2=None, aff=None, stride=1, pad=None, upsample=False
                     out_scale=out_scale, act=act, out=out, out_f32=out_f32, split_k=split_k, ln_stats=ln_stats,
                     stats_out=stats_out, gn_out=gn_out, workspace_bytes=workspace_bytes)
     cs = None
-    if gn_out and _GN_EPILOGUE and (n * Ho * Wo) % GN_SLOT_ROWS == 0 and out.dtype == torch.bfloat16 and act != ACT_GEGLU:
+    cs_ok = (n * Ho * Wo) % GN_SLOT_ROWS == 0 and out.dtype == torch.bfloat16 and act != ACT_GEGLU
+    if torch.is_tensor(gn_out):  # the caller's buffer: always filled (no silent skip)
+        assert cs_ok and pw.n_out == pw.N, "gn_out buffer: rows % 128 == 0, bf16 output, no GEGLU"
+        assert gn_out.dtype == torch.float32 and gn_out.is_contiguous() and gn_out.device == x.device and \
+            tuple(gn_out.shape) == (n * Ho * Wo // GN_SLOT_ROWS, 2, n_out), (tuple(gn_out.shape), gn_out.dtype)
+        cs = gn_out
+    elif gn_out and _GN_EPILOGUE and cs_ok:
         assert pw.n_out == pw.N
         cs = torch.empty((n * Ho * Wo // GN_SLOT_ROWS, 2, n_out), dtype=torch.float32, device=x.device)
+    if cs is not None:
         d.gn_colsum_out = _p(cs)
     # the questions are asked without the split-K workspace unless workspace_bytes names one:
     # the library splits K on its own only where it has a workspace, so a shape it would split

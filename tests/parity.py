@@ -337,7 +337,17 @@ def colsum_bound(y, slot_rows=128):
     """(ref, B), each (M / 128, 2, N), for ls_gn_colsum (colsum_pass_kernel, ls_conv.hip): per
     128-row slot the column sums of y and of y^2.  y is bf16, so y^2 is exact in fp32 (and the
     kernel's fma adds it unrounded); what rounds is the additions: 8 chains of 16 rows and the
-    8-way merge, fewer than 128 in all, any order: B = 128 2^-23 sum |terms|."""
+    8-way merge, fewer than 128 in all, any order: B = 128 2^-23 sum |terms|.
+    The other producers of ls_conv_desc.gn_colsum_out sum the same 128 stored bf16 values of a
+    slot and column in fp32, each in its own order, so the bound is theirs too when y is the
+    kernel's own stored output with its rows in slot order (halo_slot_rows):
+      * the tiled epilogue, per pass (store_tile_plain_pre: "t1 += x; t2 = fmaf(x, x, t2)" over
+        the WTM staged rows, "g1 += t1" over the slot's passes);
+      * the halo conv's register partials (CSG = 2: "q1[j] += b[j]; q2[j] = fmaf(b[j], b[j],
+        q2[j])" over a thread's stored rows, then "t1 += v.x" over the RPI threads of a column);
+      * the row-block GEMM (RB_GNCS: "t += (v >> 3) ? b * b : b" over a lane's FM rows, row16_sum
+        over the 16 lanes, merge_cs "t += part[(sl * WPS + w) * 64 + e]" over the slot's waves;
+        b * b of a bf16 b is exact in fp32, contracted to an fma or not)."""
     y = f64(y)
     M, N = y.shape
     t = y.reshape(M // slot_rows, slot_rows, N)
@@ -449,7 +459,12 @@ def stored_row_stats_bound(y, eps, chain=8):
     """(ref, B), each (rows, 2), for (mean, rstd) of the STORED bf16 rows y as a GEMM epilogue
     emits them (xattn_fused_kernel: "c1 += (b0 + b1) + (b2 + b3)", "c2 = fmaf(b0, b0, ...)" per
     32-column chunk, then double): fp32 chains of `chain` terms (8 2^-23 of sum |y|, of sum y^2),
-    fp64 from there on, var = S2 / C - mean^2 paying 2 |mean| b_mean, the casts 2^-24."""
+    fp64 from there on, var = S2 / C - mean^2 paying 2 |mean| b_mean, the casts 2^-24.
+    The same bound holds for the row-block GEMM's RB_STATS epilogue (ls_conv_rowblock.hip,
+    "cs1[i] = __builtin_amdgcn_fdot2_f32_bf16(py, one2, ...fdot2_f32_bf16(px, one2, cs1[i], ...))"
+    over the 2 fragments of a 32-column chunk, then "S1[i] += (double)cs1[i]"): a lane sums 8
+    stored values per chunk in fp32 and everything after that in double.  Where the plan reports
+    a trailing ls_row_stats pass instead (ls_conv_plan_info.row_stats), row_stats_bound applies."""
     y = f64(y)
     mu = y.mean(-1, keepdim=True)
     m2 = (y * y).mean(-1, keepdim=True)
@@ -458,6 +473,115 @@ def stored_row_stats_bound(y, eps, chain=8):
     b_m = chain * E_F32 * y.abs().mean(-1, keepdim=True)
     b_var = chain * E_F32 * m2 + 2 * mu.abs() * b_m
     return torch.cat([mu, r], -1), _slack(torch.cat([b_m + U_F32 * mu.abs(), r * (0.5 * b_var / (var + eps) + U_F32)], -1))
+
+
+def ln_fold_bound(x, stats, w, colsum, bias, rowvec=None, res=None, out_scale=1.0, out_dtype=torch.bfloat16,
+                  form="rows"):
+    """(ref, B), each (M, N), for a LayerNorm-folded linear of ls_conv2d (ln_rowstats / ln_colsum):
+
+        ref = out_scale (sum_k (x_k - mean) rstd w_k + bias + rowvec + res)      in fp64
+
+    on the operands handed to the kernel: x (M, K) bf16-rounded, stats (M, 2) the GIVEN fp32
+    (mean, rstd) rows, w (N, K) the packed bf16 weight (gamma folded, logical row order), colsum
+    (N,) the fp32 ln_colsum as handed over, bias (N,) fp32 or None, rowvec / res (M, N) or None
+    (the row each output row receives).  out_dtype None: the pre-activation value (compose with
+    act_bound / geglu_bound as for any GEMM).  The fold has two arithmetics:
+
+    form="rows": gemm_rowblock_kernel (ls_conv_rowblock.hip) normalises its register-resident A
+      rows, "v[e] = (__bf16)fmaf((float)v[e], rstd, nmr)" with "nmr = -mrow[i].x * mrow[i].y",
+      and runs a plain GEMM on them (colsum is not read).  So a = (x - mean) rstd is known to
+      ln_from_stats_bound's b_a, and
+          B = gemm_bound(ref, mag, K, out_dtype) + |out_scale| sum_k |w_k| b_a_k      (chain_linear)
+      with mag = |out_scale| (sum_k |a_k w_k| + |bias| + |rowvec| + |res|).
+
+    form="epilogue": the tiled kernels (store_tile_plain_pre "x = mr[it].y * (v[j] - mr[it].x *
+      cs[j])", store_tile_geglu "h[j] = mr[it].y * (s[j] - mr[it].x * ch[j]) + bh[j]", ln_fold8
+      "v[j] = mr.y * (v[j] - mr.x * cs[j])" for epi_chunk / epi_geglu8 / the split-K reduce)
+      accumulate the RAW rows, acc = sum_k x_k w_k, and fold afterwards.  The K accumulations
+      round at the size of sum |x_k w_k|, which a large row mean makes far larger than the
+      result: that cancellation is the form's real cost and is what the bound charges,
+          mag = |out_scale| (rstd (sum_k |x_k w_k| + |mean colsum|) + |bias| + |rowvec| + |res|)
+          B   = gemm_bound(ref, mag, K + 3, out_dtype) + |out_scale| rstd |mean| |colsum - sum_k w_k|
+      * K + 3: the product mean * colsum, the subtraction and the product with rstd are three
+        more fp32 operations on partial results no larger than mag (gemm_bound's own + 4 are the
+        bias, rowvec, residual and scale);
+      * the last term is no tolerance: the kernel subtracts mean * colsum with the fp32 colsum
+        the host summed, the reference mean * sum_k w_k exactly; their difference is computed
+        here in fp64 from the operands."""
+    x, st, w = f64(x), f64(stats), f64(w)
+    K = x.shape[1]
+    m, r = st[:, :1], st[:, 1:2]
+    s = abs(float(out_scale))
+    if form == "rows":
+        a, b_a = ln_from_stats_bound(x, stats)
+        v, mag = a @ w.T, a.abs() @ w.abs().T
+        host = None
+    elif form == "epilogue":
+        cs = f64(colsum)
+        wsum = w.sum(1)
+        v = r * (x @ w.T - m * wsum)
+        mag = r * (x.abs() @ w.abs().T + (m * cs).abs())
+        host = r * m.abs() * (cs - wsum).abs()
+    else:
+        raise ValueError(form)
+    for t in (bias, rowvec, res):
+        if t is not None:
+            v, mag = v + f64(t), mag + f64(t).abs()
+    ref, mag = v * float(out_scale), mag * s
+    if form == "rows":
+        return ref, chain_linear(gemm_bound(ref, mag, K, out_dtype), w, s * b_a)
+    return ref, gemm_bound(ref, mag, K + 3, out_dtype) + s * host
+
+
+def halo_slot_rows(plan, n_img, H, W):
+    """(M / 128, 128) int64: the output rows (pixel index (img H + y) W + x of the H x W OUTPUT
+    image) whose stored values each 128-row GroupNorm slot of gn_colsum_out sums, for the plan
+    (ops.conv_plan) of the call.  Every family but the halo kernel numbers its slots by
+    consecutive rows.  conv3x3_halo_kernel (ls_conv_halo.hip, "m0v = ... (int)(img * HW) + (tyb *
+    tpr + txb) * (TH * TW)" and store_tile_plain's "(m0 + (long)p * WTM) / CS_ROWS") numbers
+    them patch-major: TH x 16 patches (TH = plan halo_th, 16 or 8) in raster order within an
+    image, TH 16 / 128 slots per patch, a slot = 8 consecutive image rows of the patch.  Its
+    phase form (family 4, "((ph * tpc + tyb) * tpr + txb) * (TH * TW)") patches the H/2 x W/2
+    INPUT image, parity ph = 2 py + px outermost within an image, and patch pixel (r, c) is
+    stored at output pixel (2 (y0 + r) + py, 2 (x0 + c) + px)."""
+    M = n_img * H * W
+    assert M % 128 == 0
+    if plan["family"] not in (3, 4):
+        return torch.arange(M).reshape(M // 128, 128)
+    TH, TW = plan["halo_th"], 16
+    ph_form = plan["family"] == 4
+    Hp, Wp = (H // 2, W // 2) if ph_form else (H, W)  # the image the patches tile
+    tpr, tpc = Wp // TW, Hp // TH
+    lr = torch.arange(TH * TW)
+    r, c = lr // TW, lr % TW
+    out = torch.empty(M, dtype=torch.int64)
+    for img in range(n_img):
+        for ph in range(4 if ph_form else 1):
+            for tyb in range(tpc):
+                for txb in range(tpr):
+                    y, x = tyb * TH + r, txb * TW + c
+                    if ph_form:
+                        m0v = img * 4 * Hp * Wp + ((ph * tpc + tyb) * tpr + txb) * TH * TW
+                        y, x = 2 * y + (ph >> 1), 2 * x + (ph & 1)
+                    else:
+                        m0v = img * H * W + (tyb * tpr + txb) * TH * TW
+                    out[m0v + lr] = (img * H + y) * W + x
+    assert torch.equal(out.sort().values, torch.arange(M))  # every output pixel in exactly one slot
+    return out.reshape(M // 128, 128)
+
+
+def rb_chunk_counts(plan, N, M):
+    """The set of 32-column chunks per block of gemm_rowblock_kernel for the plan's grid: block
+    (rb, ns) owns chunks "[nch * ns / a.ntn, nch * (ns + 1) / a.ntn)" with nch = N / 32 (N the
+    packed width) and plan_rowblock's "ntn = max(1, min(nch, (256 + ntm - 1) / ntm))", ntm = M /
+    (128 rb_fm); ntm ntn must be the plan's grid.  One chunk: first chunk and the final
+    epilogue only; two: the odd tail; three: one steady-state pair; more: the 3-stage ring
+    wraps and the past-the-end DMA reload runs in the branch-free body."""
+    assert plan["family"] == 1
+    nch, ntm = N // 32, M // (128 * plan["rb_fm"])
+    ntn = max(1, min(nch, (256 + ntm - 1) // ntm))
+    assert ntm * ntn == plan["grid"], (ntm, ntn, plan["grid"])
+    return {nch * (ns + 1) // ntn - nch * ns // ntn for ns in range(ntn)}
 
 
 def _heads(t, n, rows, heads):

@@ -3,7 +3,9 @@ cross every tile boundary, on every compiled tile, the register-staged kernel, s
 row-block and halo kernels, the scalar (N % 8 != 0) epilogue and every epilogue operand --
 each output inside a sentinel guard band (pitch above N, extra rows), inputs checked
 unchanged, acceptance |got - ref| <= gemm_bound per element against fp64 on the same
-bf16-rounded inputs.  Every test prints its worst err/bound ratio."""
+bf16-rounded inputs.  Every test prints its worst err/bound ratio.  (The LayerNorm fold, row
+statistics out, GroupNorm column sums out and the row-block kernel's other instances and steady
+state: tests/test_gpu_edges_conv_fused.py.)"""
 import functools
 import math
 

@@ -802,3 +802,299 @@ def test_attn_bound_input_errors_cover_a_perturbation():
         worst = max(worst, P.assert_elementwise(got, ref, b - b0 * (1 - 2.0 ** -6)))  # the input terms alone
     print(f"attn_bound input errors: err/bound {worst:.3f}")
     assert worst > 0.05
+
+
+# ---------------------------------------------------------------- fused conv features
+# (tests/test_gpu_edges_conv_fused.py): the LayerNorm fold in both arithmetics, the row statistics
+# and column sums of the stored output, the affine folded into the row-block A rows
+def trunc_bf16(t):
+    return (t.float().contiguous().view(torch.int32) & -65536).view(torch.float32)
+
+
+def ln_fold_case(M, K, N, mean_sigmas, seed=0, needles=0):
+    """P.ln_case rows with their fp32 statistics, a sparse bf16 weight (its first `needles` rows
+    one-hot: output column n is a[:, 7 n] alone), the host's fp32 colsum, bias, residual."""
+    x = P.ln_case(M, K, mean_sigmas, seed)[0]
+    w = P.sparse_weight(N, K, 8, seed + N + K)
+    for n in range(needles):
+        w[n] = 0.0
+        w[n, 7 * n] = 1.0
+    w = P.bf16_round(w)
+    return dict(x=x, st=P.host_row_stats(x), w=w, colsum=w.sum(1), b=rnd(N, seed=seed + 3, scale=0.1),
+                res=P.bf16_round(rnd(M, N, seed=seed + 4)))
+
+
+def emulate_ln_fold(c, form, order="torch", st=None, drop_colsum=None, truncate_a=False, out=torch.bfloat16):
+    """Both forms of the fold in fp32.  rows: a = x rstd + (-mean rstd) rounded to bf16 (or
+    truncated), then the GEMM; epilogue: rstd (acc - mean colsum) on the raw accumulators
+    (drop_colsum: that column's colsum term left out).  st: the statistics rows the kernel uses."""
+    st = c["st"] if st is None else st
+    m, r = st[:, :1], st[:, 1:]
+    if form == "rows":
+        a = torch.addcmul(-(m * r), c["x"], r)
+        acc = mm(trunc_bf16(a) if truncate_a else bfr(a), c["w"], order)
+    else:
+        cs = c["colsum"].clone()
+        if drop_colsum is not None:
+            cs[drop_colsum] = 0.0
+        acc = r * (mm(c["x"], c["w"], order) - m * cs)
+    y = acc + c["b"] + c["res"]
+    return y if out is None else y.to(out).float()
+
+
+def ln_fold_ref(c, form, out=torch.bfloat16):
+    return P.ln_fold_bound(c["x"], c["st"], c["w"], c["colsum"], c["b"], res=c["res"], out_dtype=out, form=form)
+
+
+@pytest.mark.parametrize("form", ["rows", "epilogue"])
+@pytest.mark.parametrize("mean_sigmas", [0, 30])
+@pytest.mark.parametrize("M,K,N", [(300, 320, 72), (257, 640, 64)])
+def test_ln_fold_emulation_passes(M, K, N, mean_sigmas, form):
+    c = ln_fold_case(M, K, N, mean_sigmas)
+    for out in (torch.bfloat16, torch.float32, None):
+        ref, bound = ln_fold_ref(c, form, out)
+        for order in ("torch", "ksteps"):
+            got = emulate_ln_fold(c, form, order, out=None if out is None else out)
+            worst = P.assert_elementwise(got, ref, bound)
+        if out is not None:
+            P.assert_elementwise(ref.to(out), ref, bound)  # the rounded reference alone
+        print(f"ln fold emulation {form} {M}x{K}x{N} mean {mean_sigmas} out {out}: err/bound {worst:.3f}")
+    # rowvec and out_scale enter like the residual
+    rv = rnd(M, N, seed=9)
+    ref, bound = P.ln_fold_bound(c["x"], c["st"], c["w"], c["colsum"], c["b"], rowvec=rv, res=c["res"], out_scale=0.5, form=form)
+    got = bfr((emulate_ln_fold(c, form, out=None) + rv) * 0.5)
+    P.assert_elementwise(got, ref, bound)
+
+
+def test_ln_fold_forms_share_a_reference_and_the_host_colsum_is_charged():
+    """Both forms have one fp64 reference.  The epilogue form subtracts mean * colsum with the
+    colsum it is handed: a colsum off by 2^-12 of itself (a host that summed in bf16 steps) passes
+    the bound made with that colsum -- the host term is computed, not tolerated -- and fails the
+    bound made with the exact one."""
+    c = ln_fold_case(300, 320, 72, 30)
+    (ref_r, _), (ref_e, b_e) = ln_fold_ref(c, "rows", torch.float32), ln_fold_ref(c, "epilogue", torch.float32)
+    assert float((ref_r - ref_e).abs().max()) < 1e-9
+    worst = P.assert_elementwise(emulate_ln_fold(c, "epilogue", "ksteps", out=torch.float32), ref_e, b_e)
+    c2 = dict(c, colsum=c["colsum"] * (1 + 2.0 ** -12))
+    got = emulate_ln_fold(c2, "epilogue", out=torch.float32)
+    ref2, b2 = ln_fold_ref(c2, "epilogue", torch.float32)
+    assert torch.equal(ref2, ref_e)
+    w2 = P.assert_elementwise(got, ref2, b2)
+    with pytest.raises(AssertionError, match="err/bound"):
+        P.assert_elementwise(got, ref_e, b_e)
+    print(f"epilogue fold at 30 sigma, fp32 out: err/bound {worst:.3f}; with the host's own colsum error {w2:.3f}")
+
+
+@pytest.mark.parametrize("form", ["rows", "epilogue"])
+def test_ln_fold_neighbour_statistics_rejected(form):
+    c = ln_fold_case(257, 320, 72, 0)
+    c["x"] = P.bf16_round(rnd(257, 320, seed=3))  # rows of one distribution: the neighbour's statistics are close
+    c["st"] = P.host_row_stats(c["x"])
+    ref, bound = ln_fold_ref(c, form)
+    P.assert_elementwise(emulate_ln_fold(c, form), ref, bound)
+    r = 130
+    st = c["st"].clone()
+    st[r] = c["st"][r + 1]
+    got = emulate_ln_fold(c, form, st=st)
+    with pytest.raises(AssertionError, match=rf"\(rows \[{r}\]\)"):
+        P.assert_elementwise(got, ref, bound)
+    _rejected(got, ref, bound, f"ln fold {form}: row {r} with its neighbour's statistics")  # Frobenius lets it through
+
+
+@pytest.mark.parametrize("mean_sigmas,frobenius_passes", [(0, True), (30, False)])
+def test_ln_fold_missing_colsum_term_rejected(mean_sigmas, frobenius_passes):
+    """One column without mean * colsum[c].  At a mean near 0 the term is small and the Frobenius
+    ratio lets it through; at 30 sigma it is large enough for any check."""
+    c = ln_fold_case(300, 320, 72, mean_sigmas)
+    ref, bound = ln_fold_ref(c, "epilogue")
+    col = int((c["colsum"].abs() - 0.5).abs().argmin())  # an ordinary column (|colsum| about 0.5)
+    got = emulate_ln_fold(c, "epilogue", drop_colsum=col)
+    with pytest.raises(AssertionError, match=rf"col {col};"):
+        P.assert_elementwise(got, ref, bound)
+    ratio = (P.f64(got) - ref).abs() / bound
+    assert sorted(set(torch.nonzero(ratio > 1.0)[:, 1].tolist())) == [col]
+    fro = rel_err(got, ref)
+    print(f"missing colsum term, mean {mean_sigmas}: err/bound {float(ratio.max()):.1f}, Frobenius {fro:.2e}")
+    assert (fro < 1e-2) == frobenius_passes
+
+
+def test_ln_fold_truncated_operand_rejected():
+    """The normalised A truncated to bf16 instead of rounded: up to a whole bf16 step of a_k
+    where the bound has half of one.  The pre-activation value (out_dtype None, what geglu_bound
+    composes) rejects it on the one-hot weight rows, where the error of a_k arrives alone.  After
+    the output's own rounding to bf16 the bound has a second half step, of the OUTPUT: the defect
+    is still outside wherever bias and residual leave an output smaller than a_k.  The Frobenius
+    ratio passes either way (on record)."""
+    c = ln_fold_case(300, 320, 72, 0, needles=8)
+    ref, bound = ln_fold_ref(c, "rows", None)
+    P.assert_elementwise(emulate_ln_fold(c, "rows", out=None), ref, bound)
+    got = emulate_ln_fold(c, "rows", truncate_a=True, out=None)
+    ratio = (P.f64(got) - ref).abs() / bound
+    bad = ratio[:, :8] > 1.0
+    print(f"truncated A, pre-activation: err/bound {float(ratio.max()):.2f}, {int(bad.sum())} of {bad.numel()} needle elements outside")
+    assert float(bad.float().mean()) > 0.2 and 1.2 < float(ratio[:, :8].max()) < 2.1
+    _rejected(got, ref, bound, "ln fold rows: A truncated (pre-activation)")
+    ref16, bound16 = ln_fold_ref(c, "rows")
+    w16 = float(((P.f64(emulate_ln_fold(c, "rows", truncate_a=True)) - ref16).abs() / bound16).max())
+    print(f"truncated A, bf16 out: err/bound {w16:.2f}")
+    assert w16 > 1.2
+
+
+def emulate_stored_row_stats(y, eps, chunk_order=False):
+    """The row-block RB_STATS epilogue on the stored rows y: per 32-column chunk and lane group
+    (columns 4 lg .. + 3 of both 16-column fragments) an fp32 chain of 8, double from there."""
+    M, N = y.shape
+    t = y.reshape(M, N // 32, 2, 4, 4).permute(0, 1, 3, 2, 4).reshape(M, N // 32, 4, 8)
+    s1, s2 = torch.zeros(M, N // 32, 4), torch.zeros(M, N // 32, 4)
+    for j in range(8):
+        s1 = s1 + t[..., j]
+        s2 = (s2.double() + t[..., j].double() ** 2).float()  # fdot2 / fma: the square unrounded
+    S1, S2 = s1.double().sum((1, 2)), s2.double().sum((1, 2))
+    mean = S1 / N
+    var = (S2 / N - mean * mean).clamp_min(0.0)
+    return torch.stack([mean, 1.0 / torch.sqrt(var + eps)], 1).float()
+
+
+@pytest.mark.parametrize("N", [64, 192])
+@pytest.mark.parametrize("offset", [0.0, 3.0])
+def test_stored_row_stats_emulation_passes(N, offset):
+    y32 = rnd(300, N, seed=N) * (0.5 + rnd(300, 1, seed=1).abs()) + offset
+    y = bfr(y32)
+    ref, bound = P.stored_row_stats_bound(y, 1e-5, chain=8)
+    worst = P.assert_elementwise(emulate_stored_row_stats(y, 1e-5), ref, bound)
+    P.assert_elementwise(ref.float(), ref, bound)
+    print(f"stored row statistics N {N} offset {offset}: err/bound {worst:.3f}")
+    # the statistics of the unrounded fp32 values instead of the stored bf16 ones
+    got = emulate_stored_row_stats(y32, 1e-5)
+    with pytest.raises(AssertionError, match="err/bound"):
+        P.assert_elementwise(got, ref, bound)
+    ratio = (P.f64(got) - ref).abs() / bound
+    print(f"  from the unrounded values: err/bound {float(ratio.max()):.1f}, rows outside {int((ratio > 1).any(1).sum())} of 300, "
+          f"Frobenius {rel_err(got, ref):.2e}")
+    assert float((ratio > 1).any(1).float().mean()) > 0.9 and rel_err(got, ref) < 1e-2
+    # one row's statistics written one row further down
+    got = emulate_stored_row_stats(y, 1e-5)
+    got[200] = got[199]
+    with pytest.raises(AssertionError, match=r"row 200,"):
+        P.assert_elementwise(got, ref, bound)
+
+
+def emulate_slot_sums_csg2(t, rpi):
+    """store_tile_plain_pre's CSG = 2 form on the rows of the slots t (slots, 128, N): a thread sums
+    its rows (r0, r0 + rpi, ...) of the slot in fp32, then the rpi partials of a column in turn."""
+    S, R, N = t.shape
+    q1, q2 = torch.zeros(S, rpi, N), torch.zeros(S, rpi, N)
+    for it in range(R // rpi):
+        v = t[:, it * rpi:(it + 1) * rpi]
+        q1, q2 = q1 + v, (q2.double() + v.double() ** 2).float()
+    a1, a2 = torch.zeros(S, N), torch.zeros(S, N)
+    for r in range(rpi):
+        a1, a2 = a1 + q1[:, r], a2 + q2[:, r]
+    return torch.stack([a1, a2], 1)
+
+
+@pytest.mark.parametrize("family,th,H,W", [(3, 16, 32, 32), (3, 8, 32, 16), (4, 16, 64, 32), (4, 8, 32, 32), (0, -1, 16, 16)])
+def test_halo_slot_sums_emulation_passes(family, th, H, W):
+    """P.halo_slot_rows: every output pixel in exactly one slot, a slot = 8 rows x 16 pixels of one
+    patch (of one parity in the phase form); the CSG = 2 sums of those rows pass colsum_bound, and
+    a slot that misses one row, or sums the unrounded values, does not."""
+    n, N = 2, 40
+    plan = dict(family=family, halo_th=th)
+    rows = P.halo_slot_rows(plan, n, H, W)
+    assert rows.shape == (n * H * W // 128, 128)
+    img, yy, xx = rows // (H * W), rows % (H * W) // W, rows % W
+    step = 2 if family == 4 else 1
+    if family in (3, 4):
+        assert bool((img == img[:, :1]).all())
+        assert bool(((yy.amax(1) - yy.amin(1)) == 7 * step).all()) and bool(((xx.amax(1) - xx.amin(1)) == 15 * step).all())
+        assert bool((yy % step == yy[:, :1] % step).all()) and bool((xx % step == xx[:, :1] % step).all())  # one parity
+        # the first slot of the second image starts that image's numbering (ls_conv_halo.hip "img * HW")
+        assert int(rows[H * W // 128].min()) >= H * W
+    if family == 3 and th == 16:  # 16 x 16 patches: slot 1 is the lower half of patch 0, slot 2 starts patch 1 (x0 = 16)
+        assert rows[1, 0] == 8 * W and rows[2, 0] == 16
+    if family == 3 and th == 8:   # 8 x 16 patches on a 16-wide image: slot 1 is the patch below
+        assert rows[1, 0] == 8 * W
+    if family == 4:               # parity 1 (py 0, px 1) follows all patches of parity 0
+        assert rows[(H // 2) * (W // 2) // 128, 0] == 1
+    y32 = rnd(n * H * W, N, seed=H + W) + 1.0
+    y = bfr(y32)
+    ref, bound = P.colsum_bound(y[rows.reshape(-1)])
+    for rpi in (32, 25, 64):  # 128-column tiles (NT / 16), 160 columns (512 / 20: 25 rows per iteration of 64), narrow
+        t = y[rows.reshape(-1)].reshape(-1, 128, N)
+        if 128 % rpi:  # 64-row passes of ceil(64 / 25) iterations: pad the pass with zeros
+            t = torch.cat([t.reshape(-1, 2, 64, N), torch.zeros(t.shape[0], 2, 75 - 64, N)], 2).reshape(-1, 150, N)
+        worst = P.assert_elementwise(emulate_slot_sums_csg2(t, rpi), ref, bound)
+    print(f"slot sums family {family} th {th}: err/bound {worst:.3f}")
+    good = emulate_slot_sums_csg2(y[rows.reshape(-1)].reshape(-1, 128, N), 32)
+    bad = good.clone()
+    bad[3, 0] -= y[rows[3, 77]]
+    bad[3, 1] -= y[rows[3, 77]] ** 2
+    with pytest.raises(AssertionError, match="err/bound"):
+        P.assert_elementwise(bad, ref, bound, name="slot 3 misses a row")
+    unrounded = emulate_slot_sums_csg2(y32[rows.reshape(-1)].reshape(-1, 128, N), 32)
+    with pytest.raises(AssertionError, match="err/bound"):
+        P.assert_elementwise(unrounded, ref, bound, name="sums of the unrounded values")
+    # per-sample totals (what the suite compared before) cannot see a row that moved to the next slot
+    moved = good.clone()
+    moved[0, 0] -= y[rows[0, 77]]
+    moved[1, 0] += y[rows[0, 77]]  # (slots 0 and 1 lie in one image)
+    assert torch.allclose(moved.reshape(n, -1, 2, N).double().sum(1), good.reshape(n, -1, 2, N).double().sum(1), rtol=2e-3, atol=1e-2 * H * W)
+    with pytest.raises(AssertionError, match="err/bound"):
+        P.assert_elementwise(moved, ref, bound, name="a row summed into the next slot")
+
+
+def test_rowblock_previous_sample_affine_rejected():
+    """The row-block kernel's affine prologue (a = bf16(x scale[s] + shift[s])) with block 1 (rows
+    256 .. 511 = sample 1) reading sample 0's affine; nearly equal affines, as in the model."""
+    K, N, S, pps = 320, 64, 24, 256
+    x, scale, shift = apply_case(K, 0, S, pps, mean_sigmas=0)
+    w = P.bf16_round(P.sparse_weight(N, K, 8, 5))
+    b = rnd(N, seed=6, scale=0.1)
+    sc, sh = P.f64(scale)[:, None], P.f64(shift)[:, None]
+    a64 = P.f64(x) * sc + sh
+    a_abs = a64.abs() + 1.1 * 2.0 ** -12 * ((P.f64(x) * sc).abs() + sh.abs())  # E.conv_reference's |a'|
+    ref = (a64 @ P.f64(w).T + P.f64(b)).reshape(S * pps, N)
+    prod = (a_abs @ P.f64(w).abs().T).reshape(S * pps, N)
+    bound = P.gemm_bound(ref, prod + P.f64(b).abs(), K, torch.bfloat16, prologue=True, prod_mag=prod)
+
+    def run(sample_of):
+        a = bfr(torch.addcmul(shift[sample_of][:, None], x, scale[sample_of][:, None]))
+        return bfr(a.reshape(S * pps, K) @ w.T + b)
+
+    own = torch.arange(S)
+    worst = P.assert_elementwise(run(own), ref, bound)
+    prev = own.clone()
+    prev[1] = 0
+    got = run(prev)
+    with pytest.raises(AssertionError, match="err/bound"):
+        P.assert_elementwise(got, ref, bound)
+    ratio = ((P.f64(got) - ref).abs() / bound).amax(1)
+    bad = torch.nonzero(ratio > 1.0).reshape(-1)
+    assert int(bad.min()) >= pps and int(bad.max()) < 2 * pps
+    fro = rel_err(got, ref)
+    print(f"row-block affine: err/bound {worst:.3f}; previous sample's: {float(ratio.max()):.1f}, {bad.numel()} rows outside, Frobenius {fro:.2e}")
+    assert bad.numel() > pps // 2 and fro < 1e-2
+
+
+@pytest.mark.parametrize("M,N,K,fm,chunks", [(21760, 192, 320, 2, {1, 2}), (32768, 192, 320, 2, {3}), (4096, 2560, 320, 2, {5}),
+                                             (65536, 192, 320, 2, {6}), (32768, 64, 640, 1, {2}), (32768, 192, 640, 2, {3}),
+                                             (512, 192, 320, 2, {1}), (384, 192, 640, 1, {1})])
+def test_rb_chunk_counts(M, N, K, fm, chunks):
+    """The steady-state shapes of the GPU file against plan_rowblock's formula, and against the
+    grid the library itself plans (host only)."""
+    nch, ntm = N // 32, M // (128 * fm)
+    ntn = max(1, min(nch, -(-256 // ntm)))
+    assert P.rb_chunk_counts(dict(family=1, rb_fm=fm, grid=ntm * ntn), N, M) == chunks
+    with pytest.raises(AssertionError):
+        P.rb_chunk_counts(dict(family=1, rb_fm=fm, grid=ntm * ntn + 1), N, M)
+    from latentsync_amd import _lib, ops
+    lib = _lib.load()
+    x = torch.empty(1, 1, M, K, dtype=torch.bfloat16)
+    pw = ops.Packed(torch.empty(N, K, dtype=torch.bfloat16), None, K, 1, N)
+    lib.ls_set_tuning(15, int(fm == 2))
+    try:
+        plan = ops.conv_plan(x, pw, out=torch.empty(1, 1, M, N, dtype=torch.bfloat16), workspace_bytes=0)
+    finally:
+        lib.ls_set_tuning(15, 1)
+    assert plan["family"] == 1 and plan["rb_fm"] == fm and plan["rb_flags"] == 0, plan
+    assert P.rb_chunk_counts(plan, N, M) == chunks
