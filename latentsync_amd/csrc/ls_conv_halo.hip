@@ -26,9 +26,11 @@ namespace ls {
 //   * the 9 taps of the chunk then run from that image: tap (kh, kw) shifts the read by
 //     kh P + kw pixels (P the row pitch); the weight K-tile of each tap ([BN][64], channel-chunk-major
 //     packing) streams through an NSW-slot LDS ring by LDS-DMA, NSW - 1 taps ahead;
-//   * the halo of chunk c + 1 is loaded into registers at tap 0 of chunk c and written to
-//     the other halo image at tap 8 (so the input affine's VALU work overlaps the MFMAs
-//     of 8 taps); every wait is one constant vmcnt (padded dummy DMAs).
+//   * the halo of chunk c + 1 is loaded into registers in three batches at taps 0 / 3 / 6 of
+//     chunk c and written to the other halo image at taps 3 / 6 / 8, each batch BEHIND the
+//     MFMAs of its tap (the `tap` lambda pins the order), so the input affine's VALU work
+//     never stands between a barrier and the MFMAs whose operands are already resident;
+//     every wait is one constant vmcnt (padded dummy DMAs).
 // 8 waves as 4 (pixels) x 2 (channels), 64 x BN/2 per wave; the epilogue is
 // store_tile_plain (bias, per-frame row vector, residual, scale, GroupNorm column sums
 // of the output) with the patch's rows mapped back to image rows.
@@ -285,20 +287,32 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
   }
 
   bf16x8 apf[2][FM];  // A fragments of the current tap (both k-steps)
-  auto read_a = [&](const uint4* hb, int tt) {  // (tt compile-time after inlining)
+  auto read_a = [&](const uint4* hb, int tt, int ks) {  // (tt, ks compile-time after inlining)
     constexpr int TPR = PH ? 2 : 3;  // taps per kernel row
     const int hpt = hp0 + (tt / TPR) * P + tt % TPR;
     // the swizzle phase, shared by the wave's fragments: padded rows (P == 0 mod 8) the
     // pixel's, compact rows the halo column's (l16 + kw)
     const int sw = COMPACT ? (l16 + px + tt % TPR) & 7 : hpt & 7;
+    const int base = hpt * 8 + ((ks * 4 + lg) ^ sw);
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int base = hpt * 8 + ((ks * 4 + lg) ^ sw);
-#pragma unroll
-      for (int i = 0; i < FM; ++i)  // fragment i: + ((16 i) / TW) rows, + (16 i) % TW pixels
-        apf[ks][i] = __builtin_bit_cast(bf16x8, hb[base + 8 * (((16 * i) / TW) * P + (16 * i) % TW)]);
-    }
+    for (int i = 0; i < FM; ++i)  // fragment i: + ((16 i) / TW) rows, + (16 i) % TW pixels
+      apf[ks][i] = __builtin_bit_cast(bf16x8, hb[base + 8 * (((16 * i) / TW) * P + (16 * i) % TW)]);
   };
+  // One tap.  The order within it keeps the matrix pipe fed across the per-tap barrier:
+  //   barrier | weight fragment reads of k-step 0 | weight DMA of a later tap (under their LDS
+  //   round trip) | MFMAs of k-step 0 | A fragments of the NEXT tap's k-step 0 (into the
+  //   registers k-step 0 just released) | MFMAs of k-step 1
+  //   | the halo batch of this tap (store_halo: the GroupNorm affine + SiLU, ds_writes; then the
+  //   next batch's loads) | A fragments of the next tap's k-step 1 | next barrier
+  // sched_barrier(0) pins the seams: hipcc otherwise sinks all eight A reads behind the
+  // last MFMA, where the wave then sat out their LDS round trip in front of the barrier, and
+  // hoists the transform's VALU block in front of the MFMAs (where the source had it before).
+  // The k-step 1 A reads are the wave's last LDS instructions of the tap and need not land before the
+  // barrier (the halo image is stable within a chunk and nothing else reads their registers):
+  // the tap's closing wait is lgkmcnt(FM), not 0.  LDS instructions of a wave complete in order, so
+  // with at most FM outstanding every older one -- the weight fragment reads of the slot a later
+  // DMA overwrites, store_halo's and store_par's writes the barrier publishes -- has completed;
+  // the compiler's own counted lgkmcnt in front of the next tap's k-step 1 MFMAs covers the rest.
   auto tap = [&](int ci, int par, auto t_tag, auto last_tag) {
     constexpr int t = decltype(t_tag)::value;
     constexpr bool LAST = decltype(last_tag)::value;  // no next chunk
@@ -308,41 +322,69 @@ __global__ void __launch_bounds__((HaloCfg<TW, BN, TH_>::NT), (HaloCfg<TW, BN, T
     // of the NSW - 2 later taps and the halo batches issued at taps t - NSW + 1 .. t - 1
     // (HY only counts what may stay in flight behind the weights.  The halo registers themselves
     // are plain buffer loads: store_halo's use of them gets the compiler's own vmcnt wait -- in
-    // the phase form already one tap after the load -- so no counted wait has to cover them)
+    // the phase form already one tap after the load -- so no counted wait has to cover them.
+    // A batch's loads now stand at the end of their tap instead of behind its weight DMA; they are
+    // still younger than that DMA and older than the next tap's, so the counts are what they were)
     constexpr int HY = LAST ? 0 : (t - 1 >= 0 ? halo_issue(t - 1, NHL, GN, TS) : 0) +
                                   (NSW >= 3 && t - 2 >= 0 ? halo_issue(t - 2, NHL, GN, TS) : 0);
     if (g + NSW - 2 >= G) wait_vm<0>();  // the ring's tail
     else wait_vm<(NSW - 2) * DPT + HY>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // (t = 0 follows tap NTAP - 1, the prologue or nothing: no A reads in flight, all of it waited for)
+    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(t > 0 ? FM : 0) : "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (g + NSW - 1 < G) issue_w(g + NSW - 1, wslot(par, t + NSW - 1));
-    if constexpr (!LAST) {
-      if constexpr (GN && t == 1) store_par(ci + 1);  // read at taps 3 / 6 / 8, past a barrier
-      if constexpr (t == TS || t == 2 * TS) store_halo(hpar ^ 1, t / TS - 1);
-      if constexpr (t == 0 || t == TS || t == 2 * TS) load_halo(ci + 1, t / TS);
-    }
     const uint4* hb = hbuf + hpar * HALO;
     const uint4* wb = wbuf + wslot(par, t) * WSLOT;
-    // A fragments of tap t: at t = 0 read here; for t > 0 read at the end of tap t - 1 (the
-    // halo image is stable within a chunk), so after this tap's barrier only the weight
-    // fragments stand between the wave and its MFMAs, and the LDS array serves 10 reads per
-    // wave there instead of 18
-    if constexpr (t == 0) read_a(hb, 0);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 bfr[FN];
+    // A fragments of tap t: at t = 0 read here (the barrier above published the chunk's image);
+    // for t > 0 read during tap t - 1, so after this tap's barrier only the k-step 0 weight
+    // fragments stand between the wave and its MFMAs
+    if constexpr (t == 0) {
+      read_a(hb, 0, 0);
+      read_a(hb, 0, 1);
+    }
+    auto read_b = [&](bf16x8* bfr, int ks) {
 #pragma unroll
       for (int j = 0; j < FN; ++j)
         bfr[j] = __builtin_bit_cast(bf16x8, wb[swz64(wn * WTN + j * 16 + l16, ks * 4 + lg)]);
+    };
+    auto mfmas = [&](const bf16x8* bfr, int ks, int i0, int i1) {
 #pragma unroll
-      for (int i = 0; i < FM; ++i)
+      for (int i = i0; i < i1; ++i)
 #pragma unroll
         for (int j = 0; j < FN; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(apf[ks][i], bfr[j], acc[i][j], 0, 0, 0);
+    };
+    {
+      bf16x8 bfr0[FN], bfr1[FN];
+      read_b(bfr0, 0);
+      // the weight DMA of a later tap (about 60 issue cycles per wave instruction) under the
+      // LDS round trip of the fragment reads above, not in front of them
+      __builtin_amdgcn_sched_barrier(0);
+      if (g + NSW - 1 < G) issue_w(g + NSW - 1, wslot(par, t + NSW - 1));
+      if constexpr (!LAST) {
+        if constexpr (GN && t == 1) store_par(ci + 1);  // read at taps 3 / 6 / 8, past a barrier
+        if constexpr (t == 0) load_halo(ci + 1, 0);     // (nothing to store yet: two loads, no VALU)
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      mfmas(bfr0, 0, 0, FM - 1);
+      read_b(bfr1, 1);  // (under the last FN MFMAs of k-step 0, in front of the seam)
+      mfmas(bfr0, 0, FM - 1, FM);
+      if constexpr (t < NTAP - 1) {
+        __builtin_amdgcn_sched_barrier(0);
+        read_a(hb, t + 1, 0);
+      }
+      mfmas(bfr1, 1, 0, FM);
     }
-    if constexpr (t < NTAP - 1) read_a(hb, t + 1);
-    if constexpr (!LAST && t == NTAP - 1) store_halo(hpar ^ 1, 2);
+    if constexpr (!LAST && (t == TS || t == 2 * TS || t == NTAP - 1)) {
+      __builtin_amdgcn_sched_barrier(0);
+      store_halo(hpar ^ 1, t == NTAP - 1 ? 2 : t / TS - 1);
+      if constexpr (t < NTAP - 1) load_halo(ci + 1, t / TS);
+    }
+    if constexpr (t < NTAP - 1) {
+      __builtin_amdgcn_sched_barrier(0);
+      read_a(hb, t + 1, 1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
   };
   using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
   using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
