@@ -163,7 +163,11 @@ size_t ls_conv_workspace_bytes(const ls_conv_desc* d);
  *   6. the tiled kernels (0; 2 with an affine prologue or tuning key 1): gn_colsum_out in the
  *      epilogue where the tile has it, else by the read pass; ls_row_stats over y at the end.
  * A split-K the workspace of d cannot hold is reduced to what fits before 1. (a NULL workspace
- * is never split automatically).  Fields that do not apply to the family are -1. */
+ * is never split automatically).  Fields that do not apply to the family are -1.
+ * Within 6., a 3x3 / stride 1 / pad 1 conv with Cin % 64 == 0, no affine prologue and no split-K
+ * runs the 256-row tiles position-major (`posmajor`; tuning key 22) where that costs fewer
+ * tap-units: a tile is 256 frames at one pixel, and the taps that fall into the zero padding
+ * there are left out of its K loop.  The output is bit-identical to the standard raster's. */
 typedef struct {
   int32_t family;                  /* ls_conv_path code                                      */
   int32_t bm, bn, ks, tapu;        /* tiled kernels: tile (bm 256: the 8-wave kernels), gather */
@@ -180,9 +184,16 @@ typedef struct {
   int32_t colsum_rows;             /* the gn_colsum_out read pass over this many rows of y (0: none), */
   int32_t row_stats;               /* ls_row_stats over y                                    */
   int64_t workspace_bytes;         /* what the plan's split-K asks for, before it is fitted  */
+  int32_t posmajor;                /* tiled kernels: 1 = the position-major form of a 3x3 conv, 0 = the
+                                      standard raster (appended last: the offsets above are unchanged) */
 } ls_conv_plan_info;
 /* Host-only, no launch, no GPU needed. */
 int ls_conv_plan(const ls_conv_desc* d, ls_conv_plan_info* out);
+/* The launch order of the position-major form: block `block` of the H x W x groups x ntn grid
+ * (groups = ceil(n_img / 256) frame groups, ntn column tiles) -> out[0..3] = pixel position
+ * y * W + x, frame group, column tile, valid taps (4, 6 or 9).  The kernel runs the same
+ * function.  Host-only.  LS_ERR_INVALID: H or W < 3, groups or ntn < 1, block out of range. */
+int ls_conv_posmajor_tile(int32_t H, int32_t W, int32_t groups, int32_t ntn, int32_t block, int32_t* out);
 
 /*
  * GroupNorm statistics -> per-(sample, channel) affine for the consumer's
@@ -508,7 +519,11 @@ int ls_add_rows(const uint16_t* x, int64_t rows, int32_t C, int32_t ldx, const f
  * key 19 = the narrow 16-column halo tile for 3x3 convs with N = 8 / 16 (the VAE's conv_out with
  * conv_norm_out + SiLU fused; default on; off: the tiled 128 x 32 GEMM); key 20 = the K = 640
  * residual linears on the row-block GEMM (default off: the tiled 128 x 160 kernel), always with
- * one fragment per wave (two with the residual tile do not fit the LDS). */
+ * one fragment per wave (two with the residual tile do not fit the LDS);
+ * (key 21 is not a key: it stays LS_ERR_INVALID;)
+ * key 22 = the position-major form of the tiled 3x3 / stride 1 / pad 1 conv (ls_conv_plan_info.posmajor):
+ * 0 never, 1 where its cost model prefers it to the standard raster (default), 2 wherever it is legal
+ * (then also for calls that would run a 128-row tile; on 256 x 128 tiles for N < 256 or with key 2 = 6). */
 int ls_set_tuning(int32_t key, int32_t value);
 
 /* Diagnostics: workgroups per CU the runtime can co-schedule for a GEMM kernel

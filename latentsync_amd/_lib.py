@@ -44,7 +44,7 @@ class ConvPlanInfo(C.Structure):
     _fields_ = [(f, C.c_int32) for f in (
         "family", "bm", "bn", "ks", "tapu", "buf", "epi", "split", "rb_kt", "rb_fm", "rb_flags",
         "halo_bn", "halo_th", "halo_gn", "halo_cs", "halo_ph", "grid", "threads", "lds_bytes",
-        "reduce", "colsum_rows", "row_stats")] + [("workspace_bytes", C.c_int64)]
+        "reduce", "colsum_rows", "row_stats")] + [("workspace_bytes", C.c_int64), ("posmajor", C.c_int32)]
 
 
 class AttnDesc(C.Structure):
@@ -89,6 +89,7 @@ _SIGS = {
     "ls_conv_workspace_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
     "ls_conv_path": (C.c_int, [C.POINTER(ConvDesc)]),
     "ls_conv_plan": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvPlanInfo)]),
+    "ls_conv_posmajor_tile": (C.c_int, [C.c_int32] * 5 + [C.POINTER(C.c_int32)]),
     "ls_groupnorm": (C.c_int, [c_vp, c_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float,
                                c_vp, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
     "ls_groupnorm_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),

@@ -41,6 +41,10 @@ struct ConvArgs {
   // (Ho x Wo = H x W, M = n_img H W) over the parity's 4 taps with its [N][4 Cin] weights; the
   // host passes 1 and a 4 x larger grid, the kernel sets ph (EPI_PLAINP, tile_phase)
   int phase;
+  // position-major form of a 3x3 / stride 1 / pad 1 conv on the 256-row tiles: 0, or the number of
+  // 256-frame groups.  A tile is 256 frames at ONE pixel position (pm_tile_of), so all its rows
+  // have the same valid taps and the K loop leaves the padding taps' K-tiles out
+  int pm;
 };
 
 // Logical tile index -> (row-block, column-block), grouped: gm row-blocks x all ntn column
@@ -54,6 +58,60 @@ __device__ __forceinline__ void tile_of(const ConvArgs& a, int bid, int& tm, int
   const int first = g * a.gm, rows = min(a.ntm - first, a.gm);
   tm = first + r % rows;
   tn = r / rows;
+}
+
+// ---- position-major tiles (ConvArgs::pm): launch order.  Block b runs on XCD b % 8, and an XCD
+// hands its blocks to its CUs in index order.  The positions fall into three classes by their
+// valid taps -- 9 inside, 6 on an edge, 4 at a corner; every XCD gets a contiguous eighth of each
+// class (the remainders of the classes dealt to the XCDs in turn, so the XCDs' tap totals differ
+// by less than one tile) and runs its 9-tap tiles first, its 4-tap tiles last.  Within a class
+// the column tiles of a (frame group, position) are adjacent, then the positions of a frame
+// group: tiles running together share the A lines of neighbouring positions and the W panels in
+// the XCD's L2.  The same function is the planner's host twin (posmajor_cost, ls_conv_posmajor_tile).
+__host__ __device__ inline unsigned pm_tap_mask(int H, int W, int pos) {
+  const int yo = pos / W, xo = pos - yo * W;
+  unsigned mk = 0;
+  for (int kh = 0; kh < 3; ++kh)
+    for (int kw = 0; kw < 3; ++kw)
+      if ((unsigned)(yo - 1 + kh) < (unsigned)H && (unsigned)(xo - 1 + kw) < (unsigned)W) mk |= 1u << (kh * 3 + kw);
+  return mk;
+}
+
+// block -> (pos, frame group g, column tile tn); H, W >= 3; G frame groups, ntn column tiles
+__host__ __device__ inline void pm_tile_of(int b, int H, int W, int G, int ntn, int& pos, int& g, int& tn) {
+  const int x = b % 8;
+  int s = b / 8, off = 0;  // slot on the XCD; the XCD the class's first remainder tile goes to
+  const int pc[3] = {(H - 2) * (W - 2), 2 * (H - 2) + 2 * (W - 2), 4};
+  for (int c = 0; c < 3; ++c) {
+    const int n = pc[c] * G * ntn, q = n / 8, r = n % 8, e0 = off, e1 = off + r;  // remainders: XCDs [e0, e1) mod 8
+    const int lo = x - e0 < 0 ? 0 : x - e0;
+    const int before = e1 <= 8 ? (lo < r ? lo : r) : (x < e1 - 8 ? x : e1 - 8) + lo;
+    const int cnt = q + ((e1 <= 8 ? (x >= e0 && x < e1) : (x >= e0 || x < e1 - 8)) ? 1 : 0);
+    if (s < cnt || c == 2) {
+      const int j = x * q + before + s, t = j / ntn, qi = t % pc[c];
+      tn = j - t * ntn;
+      g = t / pc[c];
+      int yo, xo;
+      if (c == 0) {
+        yo = 1 + qi / (W - 2);
+        xo = 1 + qi % (W - 2);
+      } else if (c == 2) {
+        yo = (qi >> 1) ? H - 1 : 0;
+        xo = (qi & 1) ? W - 1 : 0;
+      } else if (qi < 2 * (W - 2)) {  // top, then bottom row
+        yo = qi < W - 2 ? 0 : H - 1;
+        xo = 1 + qi % (W - 2);
+      } else {  // left, then right column
+        const int e = qi - 2 * (W - 2);
+        yo = 1 + e % (H - 2);
+        xo = e < H - 2 ? 0 : W - 1;
+      }
+      pos = yo * W + xo;
+      return;
+    }
+    s -= cnt;
+    off = e1 % 8;
+  }
 }
 
 // K order of a 3x3 weight with Cin % 64 == 0 (packing.py): k = (ci / 64) * 576 + tap * 64 +
@@ -218,9 +276,13 @@ struct EpiSide {
 
 // tile-local row -> output row (RW: see store_tile_plain)
 constexpr int RW_PHASE = -(1 << 20);  // the tiled phase form: rows are one parity's pixels in input space
+constexpr int RW_POS = RW_PHASE - 1;  // the position-major form: rows are the frames from m0 at pixel m0r
 template <int RW>
 __device__ __forceinline__ int epi_out_row(const ConvArgs& a, int m0, long m0r, int lr) {
-  if constexpr (RW == RW_PHASE) {  // input pixel (n, y, x) of parity (py, px) -> (n Ho + 2y + py) Wo + 2x + px
+  if constexpr (RW == RW_POS) {  // (frames past the last: not stored)
+    const int n = m0 + lr;
+    return n < a.n_img ? (int)((long)n * (a.H * a.W) + m0r) : a.Mo;
+  } else if constexpr (RW == RW_PHASE) {  // input pixel (n, y, x) of parity (py, px) -> (n Ho + 2y + py) Wo + 2x + px
     const int m = m0 + lr;
     if (m >= a.M) return a.Mo;  // (past the parity's rows: not stored)
     const int hw = a.H * a.W, n = m / hw, r = m - n * hw;
@@ -289,8 +351,8 @@ __device__ __forceinline__ void store_tile_plain_pre(const ConvArgs& a, f32x4 (&
   // row vector (per-frame temb / positional-encoding rows): one row for the whole
   // tile in the common case (rows_per_vec >= the tile's row span), folded into
   // the per-column constants; otherwise looked up per row.
-  const bool rv_tile = a.rowvec && out_row(0) / a.rows_per_vec == (RW != 0 ? out_row(BM - 1)
-                                                                           : min(m0 + BM, a.M) - 1) / a.rows_per_vec;
+  const int last_row = RW == RW_POS ? out_row(min(BM, a.n_img - m0) - 1) : RW != 0 ? out_row(BM - 1) : min(m0 + BM, a.M) - 1;
+  const bool rv_tile = a.rowvec && out_row(0) / a.rows_per_vec == last_row / a.rows_per_vec;
   float bb[8], cs[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { bb[j] = 0.f; cs[j] = 0.f; }
@@ -303,7 +365,10 @@ __device__ __forceinline__ void store_tile_plain_pre(const ConvArgs& a, f32x4 (&
   }
   if (cok && a.ln_mr) load8f(a.ln_cs + col, cs);
   // no LayerNorm fold, no per-row row vector, unit output scale: the short path
-  const bool plain = !a.ln_mr && !(a.rowvec && !rv_tile) && a.out_scale == 1.f && !(a.ablate & 8);
+  // (position-major: a row vector per row is added to the column constants first, as the
+  // standard raster does for its tile -- there a 256-row tile never straddles two row vectors,
+  // posmajor_ok -- so both forms round alike)
+  const bool plain = !a.ln_mr && !(RW != RW_POS && a.rowvec && !rv_tile) && a.out_scale == 1.f && !(a.ablate & 8);
   EpiSide<ITER> cur;
   if constexpr (PRE) cur = pre;
   else if constexpr (PIPE) epi_side_load<BM, BN, WM, WN, RW>(a, m0, n0, m0r, tid, 0, cur);
@@ -332,7 +397,15 @@ __device__ __forceinline__ void store_tile_plain_pre(const ConvArgs& a, f32x4 (&
       float v[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
       float r8[8];
       unpack8(cur.rs[it], r8);
-      if (plain) {  // (block-uniform) bias (+ the tile's row vector) + residual: 2 VALU per value
+      if (RW == RW_POS && a.rowvec && !rv_tile) {  // (block-uniform)
+        float rv[8];
+        load8f(a.rowvec + rv_row(a, row) + col, rv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float b = bb[j] + rv[j];
+          v[j] = plain ? (v[j] + b) + r8[j] : (v[j] + b + 0.f + r8[j]) * a.out_scale;
+        }
+      } else if (plain) {  // (block-uniform) bias (+ the tile's row vector) + residual: 2 VALU per value
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = (v[j] + bb[j]) + r8[j];
       } else {
@@ -519,12 +592,18 @@ __device__ __forceinline__ void tile_phase(ConvArgs& a, int& z) {
   }
 }
 
-template <int BM, int BN, int WM, int WN, int EPI = EPI_ANY>
+// RW = RW_POS (the position-major form; the plan has no split-K, 16-B rows, no GEGLU): m0 is the
+// tile's first frame and m0r its pixel position.
+template <int BM, int BN, int WM, int WN, int EPI = EPI_ANY, int RW = 0>
 __device__ __forceinline__ void store_tile(const ConvArgs& a, f32x4 (&acc)[BM / WM / 16][BN / WN / 16], float* st,
-                                           int m0, int n0, int z) {
+                                           int m0, int n0, int z, long m0r = 0) {
   if constexpr (EPI == EPI_PLAIN) {
     // (the 4 x 2-wave 256-row tile keeps 64-row wave rows: column sums in its epilogue too)
-    store_tile_plain<BM, BN, WM, WN, false, BM == 256 && WM == 4>(a, acc, st, m0, n0);
+    store_tile_plain<BM, BN, WM, WN, false, BM == 256 && WM == 4, RW>(a, acc, st, m0, n0, m0r);
+    return;
+  } else if constexpr (RW == RW_POS) {
+    static_assert(EPI == EPI_ANY, "position-major: the plain or the general epilogue");
+    store_tile_plain<BM, BN, WM, WN, true, false, RW>(a, acc, st, m0, n0, m0r);
     return;
   } else if constexpr (EPI == EPI_GEGLU) {
     store_tile_geglu<BM, BN, WM, WN, false>(a, acc, st, m0, n0);
@@ -652,6 +731,9 @@ struct ConvTuning {
   // 128^2 a tie; at Cin 512 (8 chunks) the 2-slot weight ring loses to the 1-block form's 3
   // slots (13.12 -> 13.55 ms at 64^2), profiles/r05k_halo_ab.txt.  Tuning key 16 = 0: off.
   bool halo_th8 = true;
+  // ---- position-major 3x3 conv on the 256-row tiles (tuning key 22): 0 never, 1 where the
+  // cost model prefers it (posmajor_cost), 2 wherever it is legal (posmajor_ok)
+  int posmajor = 1;
 };
 extern ConvTuning g_tune;
 

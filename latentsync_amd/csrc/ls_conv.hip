@@ -1,6 +1,8 @@
 // Host side of the conv / linear layer: the plan of a call (plan_conv), the split-K reduce and
 // GroupNorm column-sum passes, and the C entry points.  The kernels are in ls_conv_tiled.hip,
 // ls_conv_big.hip, ls_conv_rowblock.hip and ls_conv_halo.hip.
+#include <algorithm>
+
 #include "ls_conv.h"
 
 namespace ls {
@@ -94,6 +96,45 @@ static void to_tiled_phase(ConvArgs& a, int bm) {
   a.M = a.n_img * a.H * a.W;
   a.ntm = cdiv(a.M, bm);
   a.gm = std::max(1, std::min(a.gm, a.ntm));
+}
+
+// The position-major form of a 3x3 / stride 1 / pad 1 conv on the 256-row tiles (ConvArgs::pm,
+// conv_gemm_big_kernel<PM>): buffer DMA over channel-chunk-major K (Cin % 64 == 0, K == 9 Cin,
+// no affine prologue), the single-pass 16-byte epilogue (no split-K, no GEGLU), images with an
+// interior (pm_tile_of).  A row vector must not change inside a standard 256-row tile, so that
+// both forms add it to the bias first and round alike (store_tile_plain_pre).  A frame group's
+// window (256 images) must fit the 31-bit byte offsets of the A descriptor.
+static bool posmajor_ok(const ls_conv_desc* d, const ConvArgs& a) {
+  const long span = 256L * a.H * a.W * std::max(a.ld1, a.C2 ? a.ld2 : 0) * 2;
+  return d->ksize == 3 && a.stride == 1 && a.pad == 1 && !a.upsample && !a.phase && a.Ho == a.H && a.Wo == a.W &&
+         a.H >= 3 && a.W >= 3 && buf_dma_ok(a, 3) && !g_tune.force_regstage && a.K == 9 * a.Cin && a.split == 1 &&
+         vec_ok(a) && a.act != LS_ACT_GEGLU && (!a.rowvec || a.rows_per_vec % 256 == 0) &&
+         span < (1L << 30);
+}
+
+// Tap-units on the critical path of the position-major launch: every XCD (32 CUs, one block
+// each) hands its blocks, in index order, to the CU that is free first.  (The standard raster
+// costs ceil(tiles / 256) * 9 in the same unit.)
+static int posmajor_cost(int H, int W, int G, int ntn) {
+  struct Memo { int H, W, G, ntn, cost; };  // (a model's few shapes recur on every call)
+  static thread_local Memo memo[8];
+  static thread_local int memo_next = 0;
+  for (const Memo& m : memo)
+    if (m.H == H && m.W == W && m.G == G && m.ntn == ntn) return m.cost;
+  const int nb = H * W * G * ntn;
+  int worst = 0;
+  for (int x = 0; x < 8; ++x) {
+    int load[32] = {0};
+    for (int b = x; b < nb; b += 8) {
+      int pos, g, tn;
+      pm_tile_of(b, H, W, G, ntn, pos, g, tn);
+      int* lo = std::min_element(load, load + 32);
+      *lo += __builtin_popcount(pm_tap_mask(H, W, pos));
+    }
+    worst = std::max(worst, *std::max_element(load, load + 32));
+  }
+  memo[memo_next++ % 8] = Memo{H, W, G, ntn, worst};
+  return worst;
 }
 
 // split-K reduction + epilogue: one thread per 8 output columns
@@ -257,7 +298,7 @@ static int plan_conv(const ls_conv_desc* d, ConvPlan& p) {
   const size_t slab = (size_t)a.M * a.N * sizeof(float);
   ls_conv_plan_info& i = p.i;
   i.bm = i.bn = i.ks = i.tapu = i.buf = i.epi = i.rb_kt = i.rb_fm = i.rb_flags = -1;
-  i.halo_bn = i.halo_th = i.halo_gn = i.halo_cs = i.halo_ph = -1;
+  i.halo_bn = i.halo_th = i.halo_gn = i.halo_cs = i.halo_ph = i.posmajor = -1;
   i.workspace_bytes = a.split > 1 ? (int64_t)(a.split * slab) : 0;
   // fewer splits where the workspace does not hold them all
   if (a.split > 1 && (!d->workspace || d->workspace_bytes < a.split * slab))
@@ -291,6 +332,29 @@ static int plan_conv(const ls_conv_desc* d, ConvPlan& p) {
     }
   }
   if (!planned) {  // the tiled kernels
+    // position-major 256-row tiles (tuning key 22): by the cost model only where the standard
+    // raster would run a 256-row tile, on that tile's width; forced (2), on 256 x 256, or 256 x 128
+    // for N < 256 or under tuning key 2 = 6
+    i.posmajor = 0;
+    if (g_tune.posmajor && posmajor_ok(d, a)) {
+      const int bn = t.bm == 256 ? t.bn : d->N >= 256 ? 256 : 128, G = cdiv(a.n_img, 256), ntn = cdiv(d->N, bn);
+      // (equal critical paths: the form with fewer tap-units in all -- the 4x4 level at 768 frames,
+      // 240 blocks either way, ran 6 % faster position-major, profiles/posmajor_kernel_ab.txt)
+      const long tiles = (long)cdiv(M, 256) * ntn;
+      const long units = ((a.H - 2L) * (a.W - 2) * 9 + (2L * (a.H - 2) + 2 * (a.W - 2)) * 6 + 16) * G * ntn;
+      const int c_pm = g_tune.posmajor == 1 && t.bm == 256 ? posmajor_cost(a.H, a.W, G, ntn) : 0;
+      const int c_std = cdiv(tiles, 256) * 9;
+      const bool take = g_tune.posmajor == 2 || (t.bm == 256 && (c_pm < c_std || (c_pm == c_std && units < tiles * 9)));
+      if (take) {
+        i.posmajor = 1;
+        t.bm = 256;
+        t.bn = bn;
+        a.pm = G;
+        a.ntm = G;
+        a.ntn = ntn;
+        a.gm = 1;
+      }
+    }
     const bool regstage = a.aff_scale || g_tune.force_regstage;  // the prologue needs the register path
     // epilogue column sums: single-pass vectorised epilogue and a tile whose staging
     // buffer holds the per-thread partials (cs_tile_fits; not 128x32 / 64x64)
@@ -308,7 +372,7 @@ static int plan_conv(const ls_conv_desc* d, ConvPlan& p) {
     i.tapu = d->ksize == 3 && Cin % 64 == 0;
     i.buf = !regstage && buf_dma_ok(a, d->ksize);
     i.epi = regstage ? -1 : epi_kind(a);
-    i.grid = a.ntm * a.ntn * (a.phase ? 4 : a.split);
+    i.grid = a.pm ? a.H * a.W * a.pm * a.ntn : a.ntm * a.ntn * (a.phase ? 4 : a.split);
     i.threads = t.bm == 256 ? 512 : 256;
     i.lds_bytes = regstage ? 0 : (int)tiled_lds(t.bm, t.bn, t.bn == 32 ? 4 : 2);
     i.reduce = a.split > 1;
@@ -328,6 +392,10 @@ extern "C" int ls_set_tuning(int32_t key, int32_t value) {
     case 18: g_tune.halo_ups = value != 0; return LS_OK;
     case 19: g_tune.halo_narrow = value != 0; return LS_OK;
     case 20: g_tune.rb640_res = value != 0; return LS_OK;
+    case 22:
+      if (value < 0 || value > 2) return fail(LS_ERR_INVALID, "position-major 3x3 conv: 0 never, 1 by the cost model, 2 wherever legal");
+      g_tune.posmajor = value;
+      return LS_OK;
     case 17:
       // (2, 32 rows per wave, was measured and rejected: DESIGN.md section 3)
       if (value != 1) return fail(LS_ERR_INVALID, "ls_ff_chain rows per wave: 1 (16) only");
@@ -371,6 +439,14 @@ extern "C" int ls_conv_plan(const ls_conv_desc* d, ls_conv_plan_info* out) {
   const int rc = plan_conv(d, p);
   if (rc == LS_OK) *out = p.i;
   return rc;
+}
+
+extern "C" int ls_conv_posmajor_tile(int32_t H, int32_t W, int32_t groups, int32_t ntn, int32_t block, int32_t* out) {
+  if (!out || H < 3 || W < 3 || groups < 1 || ntn < 1 || block < 0 || (long)block >= (long)H * W * groups * ntn)
+    return fail(LS_ERR_INVALID, "ls_conv_posmajor_tile: H, W >= 3, groups, ntn >= 1, 0 <= block < H W groups ntn");
+  pm_tile_of(block, H, W, groups, ntn, out[0], out[1], out[2]);
+  out[3] = __builtin_popcount(pm_tap_mask(H, W, out[0]));
+  return LS_OK;
 }
 
 extern "C" int ls_conv_path(const ls_conv_desc* d) {

@@ -10,8 +10,13 @@ namespace ls {
 // barrier per K-tile; the next tile's DMA is issued right after the barrier so
 // it has a whole K-tile of MFMAs to land.  MFMA runs are bracketed by
 // s_setprio(1) so the co-resident wave's fragment reads interleave.
-template <int BN, int KS, bool TAPU, int EPI, bool BUF = false>
+// PM: the position-major form of a 3x3 / stride 1 / pad 1 conv (ConvArgs::pm).  The tile is 256
+// frames at one pixel position, block -> (position, frame group, column tile) by pm_tile_of; the
+// K loop runs the K-tiles of the position's valid taps only (BufDma<PM>::next) -- the ones left
+// out added products with a zero A, so the accumulators are bit-identical to the standard raster's.
+template <int BN, int KS, bool TAPU, int EPI, bool BUF = false, bool PM = false>
 __global__ void __launch_bounds__(512) conv_gemm_big_kernel(ConvArgs a) {
+  static_assert(!PM || (KS == 3 && TAPU && BUF), "position-major: channel-chunk-major 3x3 through buffer DMA");
   constexpr int BM = 256, BK = 64, WM = 2, WN = 4;
   constexpr int WTM = BM / WM, WTN = BN / WN;
   constexpr int FM = WTM / 16, FN = WTN / 16, FH = FM / 2;
@@ -28,11 +33,16 @@ __global__ void __launch_bounds__(512) conv_gemm_big_kernel(ConvArgs a) {
   int z = bid / nt;
   bid -= z * nt;
   tile_phase<EPI>(a, z);
-  int tm, tn;
-  tile_of(a, bid, tm, tn);
+  int tm, tn, pos = 0;
+  if constexpr (PM) {  // (no split-K; the grid is positions x frame groups x column tiles)
+    z = 0;
+    pm_tile_of(blockIdx.x, a.H, a.W, a.pm, a.ntn, pos, tm, tn);  // (m0: the tile's first frame)
+  } else {
+    tile_of(a, bid, tm, tn);
+  }
   const int m0 = tm * BM, n0 = tn * BN;
   const int kt0 = z * a.kt_per_split;
-  const int kt1 = min(a.ktiles, kt0 + a.kt_per_split);
+  int kt1 = min(a.ktiles, kt0 + a.kt_per_split);
 
   int arow[AI], ach[AI], brow[BI], bch[BI];
   RowGeo geo[AI];
@@ -62,14 +72,15 @@ __global__ void __launch_bounds__(512) conv_gemm_big_kernel(ConvArgs a) {
     bch[p] = swz64(row, q % CPR) - row * CPR;
   }
   static_assert(!BUF || KS == 1 || TAPU, "buffer DMA: 1x1 or tap-major 3x3");
-  BufDma<BM, BN, AI, BI, KS> bd;  // BUF (dead code otherwise)
+  BufDma<BM, BN, AI, BI, KS, PM> bd;  // BUF (dead code otherwise)
   if constexpr (BUF) {
     int ar[AI], br[BI];
 #pragma unroll
     for (int p = 0; p < AI; ++p) ar[p] = arow[p] - m0;
 #pragma unroll
     for (int p = 0; p < BI; ++p) br[p] = brow[p] - n0;
-    bd.init(a, m0, n0, ar, ach, br, bch);
+    bd.init(a, m0, n0, ar, ach, br, bch, pos);
+    if constexpr (PM) kt1 = a.ktiles / 9 * __builtin_popcount(bd.tmask);  // (no split-K: kt0 = 0)
   }
   const int wid_u = __builtin_amdgcn_readfirstlane(wid);
   auto issue = [&](int kt, int stage) {
@@ -148,7 +159,7 @@ __global__ void __launch_bounds__(512) conv_gemm_big_kernel(ConvArgs a) {
   }
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  store_tile<BM, BN, WM, WN, EPI>(a, acc, (float*)lds, m0, n0, z);
+  store_tile<BM, BN, WM, WN, EPI, PM ? RW_POS : 0>(a, acc, (float*)lds, m0, n0, z, pos);
 }
 
 template <int BN>
@@ -159,6 +170,9 @@ static void launch_big1(const ConvPlan& p, hipStream_t s) {
     with_epi_buf<KS, TAPU>(p.i, [&](auto epi, auto buf) {
       constexpr int EPI = decltype(epi)::value;
       constexpr bool BUF = decltype(buf)::value;
+      if constexpr (KS == 3 && TAPU && BUF && (EPI == EPI_PLAIN || EPI == EPI_ANY)) {  // (posmajor_ok)
+        if (p.a.pm) return launch_plan<conv_gemm_big_kernel<BN, KS, TAPU, EPI, BUF, true>>(p, s);
+      }
       launch_plan<conv_gemm_big_kernel<BN, KS, TAPU, EPI, BUF>>(p, s);
     });
   });

@@ -51,18 +51,37 @@ __device__ __forceinline__ const void* a_src(const ConvArgs& a, int kt, int c, i
 // move AI A pieces and BI B pieces of 16 B per K-tile (LDS images lane-linear per
 // wave, 64 pieces per wave-instruction; the XOR swizzle is folded into the chunk
 // offsets ach / bch).  See conv_gemm_dma_kernel's BUF note.
-template <int BM, int BN, int AI, int BI, int KS>
+// PM: the position-major form (ConvArgs::pm) -- tile row r is frame m0 + r at pixel `pos`, and
+// next() walks only the K-tiles of the taps valid at that pixel (tmask, block-uniform).
+template <int BM, int BN, int AI, int BI, int KS, bool PM = false>
 struct BufDma {
   i32x4 rs_a1, rs_a2, rs_b;
   int avo1[AI], avo2[AI], bvo[BI];
   unsigned amask[AI];
   int tap = 0, c0 = 0;  // 3x3: tap / channel offset of the next K-tile (next())
+  unsigned tmask = 0x1FF;  // PM: the taps inside the image at the tile's pixel
 
   // arow / brow: tile-relative row of each piece; ach / bch: its logical 16-B chunk
   __device__ __forceinline__ void init(const ConvArgs& a, int m0, int n0, const int* arow, const int* ach,
-                                       const int* brow, const int* bch) {
+                                       const int* brow, const int* bch, int pos = 0) {
     const long cap = 0x7FFFFFFFL;
-    if (KS == 1) {  // (rows of one tile: the concat halves share the row index)
+    if (PM) {  // stride 1, pad 1: frame m0 + row, output pixel pos = (yo, xo), window top-left (yo - 1, xo - 1)
+      const int HWi = a.H * a.W;
+      const long base_pix = (long)m0 * HWi - a.W - 1;
+      const long tot_pix = (long)a.n_img * HWi;
+      rs_a1 = buffer_rsrc(a.x1 + base_pix * a.ld1, (uint32_t)min((tot_pix - base_pix) * a.ld1 * 2, cap));
+      rs_a2 = a.C2 ? buffer_rsrc(a.x2 + base_pix * a.ld2, (uint32_t)min((tot_pix - base_pix) * a.ld2 * 2, cap))
+                   : rs_a1;
+      tmask = pm_tap_mask(a.H, a.W, pos);
+      tap = __builtin_ctz(tmask);
+#pragma unroll
+      for (int p = 0; p < AI; ++p) {
+        const int win = arow[p] * HWi + pos;  // = frame * HWi + (yo - 1) W + xo - 1 - base_pix
+        avo1[p] = (win * a.ld1 + ach[p] * 8) * 2;
+        avo2[p] = (win * a.ld2 + ach[p] * 8) * 2;
+        amask[p] = m0 + arow[p] < a.n_img ? tmask : 0u;
+      }
+    } else if (KS == 1) {  // (rows of one tile: the concat halves share the row index)
       rs_a1 = buffer_rsrc(a.x1 + (long)m0 * a.ld1, (uint32_t)min((long)(a.M - m0) * a.ld1 * 2, cap));
       rs_a2 = a.C2 ? buffer_rsrc(a.x2 + (long)m0 * a.ld2, (uint32_t)min((long)(a.M - m0) * a.ld2 * 2, cap)) : rs_a1;
 #pragma unroll
@@ -144,6 +163,16 @@ struct BufDma {
       k.tap = 0;
       k.two = a.C2 && kt * 64 >= a.C1;  // concat: a K-tile lies in one source (host: C1 % 64 == 0)
       k.soff_a = k.two ? (kt * 64 - a.C1) * 2 : kt * 128;
+    } else if (PM) {  // the valid taps of each chunk in turn (kt only counts them)
+      const int kh = tap / 3, kw = tap - kh * 3;
+      k.tap = tap;
+      k.two = c0 >= a.C1;
+      const int ld = k.two ? a.ld2 : a.ld1;
+      k.soff_a = ((kh * a.W + kw) * ld + (k.two ? c0 - a.C1 : c0)) * 2;
+      k.soff_b = ((c0 >> 6) * 9 + tap) * 128;
+      const unsigned rest = tmask & (0x1FEu << tap);  // the chunk's valid taps after this one
+      if (rest) tap = __builtin_ctz(rest);
+      else { tap = __builtin_ctz(tmask); c0 += 64; }
     } else if (a.phase) {  // (uniform) the parity's 4 taps per chunk: tap and channel straight from kt
       int cc;
       k.tap = tap_of(a, kt * 64, cc);
