@@ -860,6 +860,71 @@ size_t ls_gif_lzw_workspace_bytes(int32_t n, int32_t H, int32_t W);
 int ls_gif_lzw(const uint8_t* idx, int32_t n, int32_t H, int32_t W, uint8_t* out, int64_t out_capacity,
                int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- classic SyncNet evaluation (additive, ABI stays 14) ------------------------------ */
+
+/* python_speech_features.mfcc(signal, 16000) with that library's defaults, from its
+ * definition (the library is not a dependency; parity with it is unpinned): audio fp32 mono
+ * 16 kHz [n] on the INT16 SCALE -> out fp32 [13][T] coefficient-major, T = 1 + ceil((n - 400)
+ * / 160) for n > 400, else 1.  Pre-emphasis y[0] = x[0], y[i] = x[i] - 0.97 x[i-1]; frames of
+ * 400 every 160, the tail zero-padded, rectangular window; |rfft(frame, 512)|^2 / 512; the
+ * frame energy = its sum; filters fp32 [26][257] (latentsync_amd.synceval.mfcc_filters); a
+ * zero energy becomes 2^-52; log; DCT-II ("ortho"), coefficients 0..12; lifter 1 + 11 sin(pi
+ * k / 22); coefficient 0 = log(frame energy).  fp32 throughout, a direct DFT against a
+ * twiddle table.  One launch, no workspace.  LS_ERR_INVALID, nothing launched: null
+ * pointers, n < 1 or above 2^38. */
+int ls_mfcc(const float* audio, int64_t n, const float* filters, float* out, void* stream);
+
+/* Convolution over (time, y, x) as an implicit GEMM on v_mfma_f32_16x16x32_bf16, fp32
+ * accumulate, for the windows ls_conv2d and ls_conv3x3_strided do not have: x bf16
+ * [T][H][W][Cin] pitch ldx,
+ *   y[t, oy, ox, n] = act(bias[n] + sum_{it, iy, ix, ci} x[t + it, oy stride_h - pad_h + iy,
+ *                                                         ox stride_w - pad_w + ix, ci] w[n, it, iy, ix, ci])
+ * for t < T - kt + 1, oy < Ho = (H + 2 pad_h - kh) / stride_h + 1, ox < Wo likewise; a tap in
+ * the spatial padding reads zero; temporal stride 1, no temporal padding.  y is bf16
+ * [T - kt + 1][Ho][Wo] pitch ldy, or fp32 with y_f32 = 1 (ldy in elements); act 0 none, 1
+ * ReLU; bias fp32 [N] or NULL.  w is bf16 [N][K], k = ((it kh + iy) kw + ix) Cin + ci, K =
+ * kt kh kw Cin rounded up to 64 with zero columns (packing.pack_weight_general).  With kt = 1
+ * the T steps are independent images; a linear is kt = kh = kw = H = W = 1.  Any M (also
+ * below 16) and any N.  The kernel form is chosen from K and N alone, so a result does not
+ * depend on how many steps are computed together.  LS_ERR_INVALID, nothing launched: null
+ * x / w / y, kt outside 1..5, kh or kw outside 1..7, a stride outside 1..2, a pad outside
+ * 0..1, act or y_f32 outside 0..1, Cin % 8, ldx % 8, ldx < Cin, ldy < N, a bf16 ldy % 8, K
+ * not that of the window, a window that does not fit (T < kt, H + 2 pad_h < kh, ...),
+ * x / w / bf16 y not 16-byte aligned. */
+int ls_conv_general(const uint16_t* x, int32_t ldx, int32_t T, int32_t H, int32_t W, int32_t Cin,
+                    const uint16_t* w, int32_t K, int32_t N, const float* bias, int32_t kt, int32_t kh, int32_t kw,
+                    int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w, int32_t act, void* y,
+                    int32_t ldy, int32_t y_f32, void* stream);
+
+/* Max-pool of bf16 NHWC [n_img][H][W][C] pitch ldx -> [n_img][Ho][Wo][C] pitch ldy, Ho =
+ * (H + 2 pad_h - kh) / stride_h + 1: window 1..3, stride 1..2, pad 0..1 per axis (at most half
+ * the window); the padding is -inf and never wins.  Exact.  LS_ERR_INVALID, nothing
+ * launched: null pointers, a window / stride / pad outside those ranges, C % 8, a pitch % 8
+ * or below C, a window that does not fit, pointers not 16-byte aligned. */
+int ls_maxpool2d(const uint16_t* x, int32_t ldx, int32_t n_img, int32_t H, int32_t W, int32_t C, int32_t kh,
+                 int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w, uint16_t* y,
+                 int32_t ldy, void* stream);
+
+/* calc_pdist of syncnet_eval.py and its mean: im_feat, cc_feat fp32 [n][D] ->
+ *   dists[i][j] = | im_feat[i] - ccp[i + j] + 1e-6 |_2   (F.pairwise_distance), fp32 [n][2 vshift + 1],
+ * ccp = cc_feat with vshift rows of zeros at each end, and mean_dists[j] = mean_i dists[i][j],
+ * fp32 [2 vshift + 1].  Every sum runs in a fixed order: the result is deterministic.  Two
+ * launches.  LS_ERR_INVALID: null pointers, n outside 1..2^24, D < 1, vshift outside 0..15. */
+int ls_sync_offset(const float* im_feat, const float* cc_feat, int32_t n, int32_t D, int32_t vshift, float* dists,
+                   float* mean_dists, void* stream);
+
+/* SyncNetDetector.crop_video's per-frame crop: frames uint8 RGB [n][H][W][3]; plan int32
+ * [n][5] = (y0, y1, x0, x1, bsi) on the device.  Frame i is padded by bsi on every side with
+ * the value 110, cropped to rows y0 .. y1 - 1 and columns x0 .. x1 - 1 of the padded frame and
+ * resized to 224 x 224 as cv2.resize does by default for uint8 (INTER_LINEAR: 11-bit
+ * fixed-point coefficients, two rounding passes; a 448 x 448 crop takes the 2 x 2 area mean)
+ * -> out uint8 [n][224][224][3].  Written from OpenCV's definition; cv2 is not a dependency
+ * and parity with it is unpinned.  A position outside the frame reads 110 wherever it lies;
+ * an empty crop (the host refuses it) is written as zeros.  LS_ERR_INVALID: null pointers,
+ * n < 1, a frame size outside 1..32768. */
+int ls_crop_track(const uint8_t* frames, int32_t n, int32_t H, int32_t W, const int32_t* plan, uint8_t* out,
+                  void* stream);
+
 int ls_abi_version(void);
 const char* ls_last_error(void);
 

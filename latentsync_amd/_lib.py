@@ -167,6 +167,12 @@ _SIGS = {
     "ls_gif_strip_rows": (C.c_int, []),
     "ls_gif_lzw_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "ls_gif_lzw": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, C.c_int64, c_vp, c_vp, C.c_size_t, c_vp]),
+    "ls_mfcc": (C.c_int, [c_vp, C.c_int64, c_vp, c_vp, c_vp]),
+    "ls_conv_general": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_vp, C.c_int32,
+                                  C.c_int32, c_vp] + [C.c_int32] * 8 + [c_vp, C.c_int32, C.c_int32, c_vp]),
+    "ls_maxpool2d": (C.c_int, [c_vp] + [C.c_int32] * 11 + [c_vp, C.c_int32, c_vp]),
+    "ls_sync_offset": (C.c_int, [c_vp, c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, c_vp, c_vp]),
+    "ls_crop_track": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, c_vp, c_vp]),
 }
 
 EXPORTED = tuple(_SIGS)

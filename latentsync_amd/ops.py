@@ -952,3 +952,100 @@ def gif_lzw(idx_u8, workspace=None, capacity=None):
                 return out[:total], offsets
             capacity = total
     raise RuntimeError("gif_lzw: the coded size changed between two runs on the same frames")
+
+
+# ---- classic SyncNet evaluation (synceval.py; csrc/ls_synceval.hip) ---------------------
+
+
+class PackedGeneral:
+    """An operand of ls_conv_general: w bf16 (N, K) (packing.pack_weight_general), bias fp32
+    (N,) or None, the window (kt, kh, kw) and the padded input channel count."""
+
+    def __init__(self, w, bias, cin, window):
+        self.w, self.bias, self.cin, self.window = w, bias, cin, tuple(window)
+        self.N, self.K = w.shape
+
+
+def mfcc(audio_i16scale, filters, out=None):
+    """python_speech_features.mfcc's defaults (ls_mfcc): fp32 (n,) mono 16 kHz samples on the
+    int16 scale, filters fp32 (26, 257), both on the device -> fp32 (13, T)."""
+    lib = _lib.load()
+    a = audio_i16scale
+    if a.dim() != 1 or a.dtype != torch.float32 or not a.is_cuda or not a.is_contiguous() or a.numel() < 1:
+        raise ValueError(f"mfcc: a non-empty contiguous fp32 1-D device tensor expected, got {a.dtype} "
+                         f"{tuple(a.shape)} on {a.device}")
+    assert tuple(filters.shape) == (26, 257) and filters.dtype == torch.float32 and filters.is_contiguous()
+    n = a.numel()
+    T = 1 + -(-(n - 400) // 160) if n > 400 else 1
+    if out is None:
+        out = torch.empty((13, T), dtype=torch.float32, device=a.device)
+    assert tuple(out.shape) == (13, T) and out.is_contiguous() and out.dtype == torch.float32
+    check(lib.ls_mfcc(_p(a), n, _p(filters), _p(out), _stream()), "ls_mfcc")
+    return out
+
+
+def conv_out_hw(H, W, window, stride, pad):
+    return (H + 2 * pad[0] - window[-2]) // stride[0] + 1, (W + 2 * pad[1] - window[-1]) // stride[1] + 1
+
+
+def conv_general(x, pw: PackedGeneral, stride=(1, 1), pad=(0, 0), relu=False, out=None, out_f32=False):
+    """ls_conv_general: x (T, H, W, Cin) bf16 NHWC -> (T - kt + 1, Ho, Wo, N) bf16 (fp32 with
+    out_f32), the window of ``pw`` over (time, y, x), ReLU on request.  ``out`` may be a
+    pitched NHWC view."""
+    lib = _lib.load()
+    T, H, W, Cin = x.shape
+    kt, kh, kw = pw.window
+    assert pw.cin == Cin and x.dtype == torch.bfloat16, (pw.cin, Cin, x.dtype)
+    Ho, Wo = conv_out_hw(H, W, pw.window, stride, pad)
+    dt = torch.float32 if out_f32 else torch.bfloat16
+    if out is None:
+        out = torch.empty((T - kt + 1, Ho, Wo, pw.N), dtype=dt, device=x.device)
+    assert tuple(out.shape) == (T - kt + 1, Ho, Wo, pw.N) and out.dtype == dt, (tuple(out.shape), out.dtype)
+    check(lib.ls_conv_general(_p(x), _ld(x), T, H, W, Cin, _p(pw.w), pw.K, pw.N, _p(pw.bias), kt, kh, kw, stride[0],
+                              stride[1], pad[0], pad[1], int(bool(relu)), _p(out), _ld(out), int(out_f32), _stream()),
+          "ls_conv_general")
+    return out
+
+
+def maxpool2d(x, window, stride, pad=(0, 0), out=None):
+    """ls_maxpool2d: x (n, H, W, C) bf16 NHWC -> (n, Ho, Wo, C); the padding is -inf."""
+    lib = _lib.load()
+    n, H, W, C_ = x.shape
+    Ho, Wo = conv_out_hw(H, W, window, stride, pad)
+    if out is None:
+        out = torch.empty((n, Ho, Wo, C_), dtype=torch.bfloat16, device=x.device)
+    assert tuple(out.shape) == (n, Ho, Wo, C_) and out.dtype == x.dtype == torch.bfloat16
+    check(lib.ls_maxpool2d(_p(x), _ld(x), n, H, W, C_, window[0], window[1], stride[0], stride[1], pad[0], pad[1],
+                           _p(out), _ld(out), _stream()), "ls_maxpool2d")
+    return out
+
+
+def sync_offset(im_feat, cc_feat, vshift, dists=None, mean_dists=None):
+    """calc_pdist and its mean (ls_sync_offset): im_feat, cc_feat fp32 (n, D) contiguous ->
+    (dists fp32 (n, 2 vshift + 1), mean_dists fp32 (2 vshift + 1,))."""
+    lib = _lib.load()
+    n, D = im_feat.shape
+    assert tuple(cc_feat.shape) == (n, D) and im_feat.dtype == cc_feat.dtype == torch.float32
+    assert im_feat.is_contiguous() and cc_feat.is_contiguous()
+    win = 2 * int(vshift) + 1
+    if dists is None:
+        dists = torch.empty((n, win), dtype=torch.float32, device=im_feat.device)
+    if mean_dists is None:
+        mean_dists = torch.empty((win,), dtype=torch.float32, device=im_feat.device)
+    assert tuple(dists.shape) == (n, win) and dists.is_contiguous() and mean_dists.is_contiguous()
+    check(lib.ls_sync_offset(_p(im_feat), _p(cc_feat), n, D, int(vshift), _p(dists), _p(mean_dists), _stream()),
+          "ls_sync_offset")
+    return dists, mean_dists
+
+
+def crop_track(frames_u8, plan, out=None):
+    """ls_crop_track: frames uint8 (n, H, W, 3) and plan int32 (n, 5) = (y0, y1, x0, x1, bsi),
+    both on the device -> uint8 (n, 224, 224, 3)."""
+    lib = _lib.load()
+    n, H, W = _rgb_frames(frames_u8, "crop_track")
+    assert tuple(plan.shape) == (n, 5) and plan.dtype == torch.int32 and plan.is_cuda and plan.is_contiguous()
+    if out is None:
+        out = torch.empty((n, 224, 224, 3), dtype=torch.uint8, device=frames_u8.device)
+    assert tuple(out.shape) == (n, 224, 224, 3) and out.dtype == torch.uint8 and out.is_contiguous()
+    check(lib.ls_crop_track(_p(frames_u8), n, H, W, _p(plan), _p(out), _stream()), "ls_crop_track")
+    return out

@@ -195,3 +195,32 @@ def pack_xattn_wo(wo: torch.Tensor, heads: int = 8):
     out = torch.empty_like(w)
     out[:, :, :, rows[:, None], phys, :] = w
     return out.contiguous()
+
+
+def pack_weight_general(w: torch.Tensor, cin_pad: int = None) -> torch.Tensor:
+    """w (O, I) linear, (O, I, kh, kw) or (O, I, kt, kh, kw) fp32 -> fp32 (O, K) for
+    ls_conv_general: always tap-major, k = ((it kh + iy) kw + ix) I' + ci with I' = I rounded
+    up to 8 (or cin_pad) by zero channels, K rounded up to 64 by zero columns."""
+    w = w.float()
+    if w.dim() == 2:
+        w = w[:, :, None, None, None]
+    elif w.dim() == 4:
+        w = w[:, :, None]
+    O, I, kt, kh, kw = w.shape
+    ip = cin_pad or _r8(I)
+    assert ip >= I and ip % 8 == 0, (ip, I)
+    if ip != I:
+        w = torch.cat([w, torch.zeros(O, ip - I, kt, kh, kw, dtype=w.dtype)], 1)
+    w = w.permute(0, 2, 3, 4, 1).reshape(O, kt * kh * kw * ip)
+    K = _r64(w.shape[1])
+    if K != w.shape[1]:
+        w = torch.cat([w, torch.zeros(O, K - w.shape[1], dtype=w.dtype)], 1)
+    return w.contiguous()
+
+
+def unpack_weight_general(p: torch.Tensor, cin: int, window, cin_pad: int = None) -> torch.Tensor:
+    """The inverse of pack_weight_general: (O, K) -> (O, cin, kt, kh, kw)."""
+    kt, kh, kw = window
+    ip = cin_pad or _r8(cin)
+    O = p.shape[0]
+    return p[:, :kt * kh * kw * ip].reshape(O, kt, kh, kw, ip).permute(0, 4, 1, 2, 3)[:, :cin].contiguous()

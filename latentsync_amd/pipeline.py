@@ -70,6 +70,25 @@ def load_data_pth(data_path):
     return data
 
 
+def load_face_boxes(face_boxes):
+    """A path to a .npy, an array or a tensor -> float64 (N, 4) numpy of x1, y1, x2, y2 (an
+    undetected frame all NaN).  ValueError for a wrong shape, infinities or a partly-NaN row."""
+    if isinstance(face_boxes, (str, bytes)) or hasattr(face_boxes, "__fspath__"):
+        face_boxes = np.load(face_boxes, allow_pickle=False)
+    if hasattr(face_boxes, "detach"):
+        face_boxes = face_boxes.detach().cpu().numpy()
+    b = np.asarray(face_boxes)
+    if b.ndim != 2 or b.shape[1] != 4 or b.shape[0] < 1 or b.dtype.kind not in "fiu":
+        raise ValueError(f"face_boxes: a numeric (N, 4) array of x1, y1, x2, y2 expected, got {b.dtype} {b.shape}")
+    b = b.astype(np.float64)
+    nan = np.isnan(b)
+    if (nan.any(axis=1) & ~nan.all(axis=1)).any():
+        raise ValueError("face_boxes: a frame's row is partly NaN (a frame without a detection is all NaN)")
+    if np.isinf(b).any():
+        raise ValueError("face_boxes: infinite coordinates")
+    return b
+
+
 def read_video_frames(video_path, video_fps=None, device=None):
     """Original video frames for restore_video: read_video (util.py:46-100) decodes
     with ffmpeg/cv2, which this build does not carry, so the frames come already
@@ -533,8 +552,27 @@ class LipsyncPipeline:
         set and an .npz output gains ``sync_scores`` and ``sync_conf``; an .avi is unchanged.
         ``thumbnail_path=`` writes the reference's GIF thumbnail (thumbnail.py) of the frames the
         writer writes, made on the device just before them, with ``thumbnail_text`` as its
-        subtitle, ``thumbnail_duration`` (6) and ``thumbnail_fps`` (3) as api.py:168-174 sets."""
+        subtitle, ``thumbnail_duration`` (6) and ``thumbnail_fps`` (3) as api.py:168-174 sets.
+        ``sync_eval=`` (a synceval.SyncNetEval on this device) with ``face_boxes=`` (a .npy path or
+        an (N, 4) array of x1, y1, x2, y2 detector boxes in frame coordinates, one row per frame
+        of data.pth, an undetected interior frame all NaN) runs the reference's quality gate
+        (eval/eval_sync_conf.py) on the frames about to be written: they are cropped about the
+        boxes (synceval.crop_track) and evaluated against the request's audio (sync_evaluation).
+        last_av_offset / last_lse_d / last_lse_c are set and an .npz output gains ``av_offset``,
+        ``lse_d`` and ``lse_c``; an .avi is unchanged."""
         from . import repeat as rep
+        face_boxes = None
+        if kwargs.get("sync_eval") is not None:
+            if kwargs.get("face_boxes") is None:
+                raise ValueError("sync_eval= needs face_boxes=: the evaluation runs on a 224 x 224 crop track about "
+                                 "the detector's boxes, and this build carries no face detector (a .npy path or an "
+                                 "(N, 4) array of x1, y1, x2, y2 in frame coordinates)")
+            if kwargs.get("faces_only"):
+                raise ValueError("sync_eval with faces_only=True: the evaluation works on the restored frames and "
+                                 "face_boxes are in frame coordinates")
+            if abs(float(video_fps) - 25.0) > 1e-6:
+                raise ValueError(f"sync_eval: the evaluation is defined at 25 frames/s, not {video_fps}")
+            face_boxes = load_face_boxes(kwargs["face_boxes"])
         # write_video's brightness restore runs only `if use_darken and brightness_factor`
         # (util.py:150-151, reached from :594).  It runs on the device (darken.py) from the
         # caller's per-frame FaceMesh landmarks -- the face-mesh model is not carried -- so
@@ -568,6 +606,8 @@ class LipsyncPipeline:
         faces, boxes, affine_matrices = data["faces"], list(data["boxes"]), list(data["affine_matrices"])
         if landmarks is not None and len(landmarks) != len(faces):
             raise ValueError(f"face_landmarks: {len(landmarks)} landmark rows for {len(faces)} faces in {data_path}")
+        if face_boxes is not None and len(face_boxes) != len(faces):
+            raise ValueError(f"face_boxes: {len(face_boxes)} box rows for {len(faces)} faces in {data_path}")
         # the original frames are read up front (:405) because they are repeated /
         # truncated together with the faces, boxes and matrices below; only rank 0
         # restores and writes, so the other ranks never decode or hold them
@@ -578,6 +618,9 @@ class LipsyncPipeline:
         if landmarks is not None and rank0 and video_frames is None:
             raise ValueError(f"use_darken: {video_path} yields no frames, so there are no restored frames to "
                              "brighten (face_landmarks are in frame coordinates)")
+        if face_boxes is not None and rank0 and video_frames is None:
+            raise ValueError(f"sync_eval: {video_path} yields no frames, so there are no restored frames to "
+                             "evaluate (face_boxes are in frame coordinates)")
         R = height or faces.shape[-1]
         self.check_inputs(R, width or R, callback_steps)
         # faces stored at another resolution are resized to R in run_windows, as the
@@ -592,8 +635,10 @@ class LipsyncPipeline:
 
         def per_frame(fn, n):
             """Apply a repeat/truncate to every per-frame sequence together (:448-452, :462-466)."""
-            nonlocal faces, boxes, affine_matrices, video_frames, landmarks
+            nonlocal faces, boxes, affine_matrices, video_frames, landmarks, face_boxes
             faces, boxes, affine_matrices = fn(faces, n), fn(boxes, n), fn(affine_matrices, n)
+            if face_boxes is not None:
+                face_boxes = fn(face_boxes, n)
             if landmarks is not None:
                 landmarks = fn(landmarks, n)
             if video_frames is not None:
@@ -632,6 +677,9 @@ class LipsyncPipeline:
                 frames_out = darken.enhance_face_brightness(frames_out.contiguous(), np.asarray(landmarks[:n_fr]),
                                                             brightness_factor)
         n_out = frames_out.shape[0]
+        gate = None
+        if face_boxes is not None:
+            gate = self.sync_evaluation(kwargs["sync_eval"], frames_out, face_boxes[:n_out], audio_path, video_fps)
         if video_out_path.endswith(".avi"):
             # a playable file: Motion-JPEG encoded on the device + PCM audio (video.py).  An
             # AVI has no side channel for padding_duration, so the reference's trim of the
@@ -650,6 +698,8 @@ class LipsyncPipeline:
         self._thumbnail(frames_out, video_fps, kwargs)
         audio_keep = int(n_out / video_fps * audio_sample_rate)
         extra = {} if sync is None else dict(sync_scores=sync.numpy(), sync_conf=np.float32(self.last_sync_conf))
+        if gate is not None:
+            extra.update(av_offset=np.int64(gate[0]), lse_d=np.float32(gate[1]), lse_c=np.float32(gate[2]))
         np.savez(video_out_path if video_out_path.endswith(".npz") else video_out_path + ".npz",
                  frames=frames_out.cpu().numpy(), audio=np.asarray(audio_samples[:audio_keep]),
                  fps=video_fps, sample_rate=audio_sample_rate, padding_duration=padding_duration, **extra)
@@ -683,3 +733,21 @@ class LipsyncPipeline:
         self.last_sync_scores = scores.float().cpu()
         self.last_sync_conf = float(self.last_sync_scores.mean()) if scores.numel() else float("nan")
         return self.last_sync_scores
+
+    def sync_evaluation(self, net, frames_u8, face_boxes, audio_path, video_fps=25):
+        """The reference's quality gate on a result (synceval.py; eval/eval_sync_conf.py): the
+        frames (uint8 (n, H, W, 3) on the device) cropped about face_boxes to the 224 x 224 track,
+        against the request's audio at 16 kHz, zero-padded or cut to n / video_fps seconds as
+        sync_confidence does.  The evaluation is defined at 25 frames/s.  Sets last_av_offset
+        (frames), last_lse_d (min_dist) and last_lse_c (conf) and returns the three."""
+        from . import synceval as se
+        from .audio import read_audio
+        if abs(float(video_fps) - 25.0) > 1e-6:
+            raise ValueError(f"sync_eval: the evaluation is defined at 25 frames/s, not {video_fps}")
+        n = frames_u8.shape[0]
+        wav = read_audio(audio_path, se.SAMPLE_RATE).float()
+        want = int(n / video_fps * se.SAMPLE_RATE)
+        wav = wav[:want] if wav.numel() >= want else torch.cat([wav, torch.zeros(want - wav.numel())])
+        track = se.crop_track(frames_u8.to(net.device).contiguous(), face_boxes)
+        self.last_av_offset, self.last_lse_d, self.last_lse_c = net.evaluate(frames=track, audio=wav)
+        return self.last_av_offset, self.last_lse_d, self.last_lse_c
