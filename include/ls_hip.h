@@ -925,6 +925,84 @@ int ls_sync_offset(const float* im_feat, const float* cc_feat, int32_t n, int32_
 int ls_crop_track(const uint8_t* frames, int32_t n, int32_t H, int32_t W, const int32_t* plan, uint8_t* out,
                   void* stream);
 
+/* ---- S3FD face detector of the sync gate (additive, ABI stays 14) ---------------------- */
+
+/* S3FD.detect_faces' input preparation: frames uint8 RGB [n][H][W][3] -> out bf16 [n][h][w][8],
+ * h = round(H s), w = round(W s) (cvRound: half to even), resized as cv2.resize(image, (0, 0),
+ * fx = s, fy = s, INTER_LINEAR) does for uint8 -- source step 1 / s on both axes, ls_crop_track's
+ * 11-bit coefficients and two rounding passes; s = 1 copies -- minus the channel means: channel
+ * 0 = R - 123, 1 = G - 117, 2 = B - 104 (the reference's two [2, 1, 0] swaps cancel), channels
+ * 3..7 zero.  Integers below 256 in magnitude: exact in bf16.  Written from OpenCV's
+ * definition; parity with cv2 itself is unpinned.  LS_ERR_INVALID, nothing launched: null
+ * pointers, n < 1, a frame size outside 1..32768, s outside (0, 1], s = 0.5 (cv2 takes its
+ * 2 x 2 area path there, which is not restated), an empty scaled frame, out not 16-byte
+ * aligned. */
+int ls_s3fd_prep(const uint8_t* frames, int32_t n, int32_t H, int32_t W, double s, uint16_t* out, void* stream);
+
+/* The VGG trunk's convolution: 3 x 3, stride 1, padding = dilation (1 or 6), bias, ReLU, on
+ * v_mfma_f32_16x16x32_bf16 with fp32 accumulation; x bf16 [n_img][H][W][Cin] pitch ldx -> y bf16
+ * [n_img][H][W][N] pitch ldy.  w is bf16 [N][9 Cin], k = (iy 3 + ix) Cin + ci
+ * (packing.pack_weight_general of a 3 x 3 weight: ls_conv_general takes the same operand).  A
+ * block owns 128 pixels x 64 channels and stages each (tap, 64-channel chunk) of w in LDS; a
+ * tap in the padding is a zero operand and never a load, and a tap that is padding for a whole
+ * block is skipped with its weights.  One kernel form for every shape, and a pixel's sum runs
+ * in one fixed order: an image's result does not depend on n_img.  bias fp32 [N] or NULL.
+ * LS_ERR_INVALID, nothing launched: null x / w / y, dilation not 1 or 6, Cin not a multiple of
+ * 64 in 64..1024, N not a multiple of 64, a pitch % 8 or below its channel count, n_img / H / W
+ * below 1, x / w / y not 16-byte aligned. */
+int ls_conv3x3_relu(const uint16_t* x, int32_t ldx, int32_t n_img, int32_t H, int32_t W, int32_t Cin,
+                    const uint16_t* w, int32_t N, const float* bias, int32_t dilation, uint16_t* y, int32_t ldy,
+                    void* stream);
+
+/* MaxPool2d(2, 2, ceil_mode = True) of bf16 NHWC [n_img][H][W][C] pitch ldx -> [n_img][Ho][Wo][C]
+ * pitch ldy, Ho = ceil(H / 2), Wo = ceil(W / 2); the last window of an odd axis is clipped to
+ * the image.  Exact.  LS_ERR_INVALID, nothing launched: null pointers, C % 8, a pitch % 8 or
+ * below C, n_img / H / W below 1, pointers not 16-byte aligned. */
+int ls_maxpool2x2_ceil(const uint16_t* x, int32_t ldx, int32_t n_img, int32_t H, int32_t W, int32_t C, uint16_t* y,
+                       int32_t ldy, void* stream);
+
+/* L2Norm.forward per pixel in fp32: y[p, c] = x[p, c] / (sqrt(sum_c x[p, c]^2) + 1e-10) weight[c];
+ * x bf16 [M][C] pitch ldx -> y bf16 [M][C] pitch ldy, weight fp32 [C].  An all-zero row gives
+ * zeros.  LS_ERR_INVALID, nothing launched: null pointers, C outside 8..8192 or % 8, a pitch %
+ * 8 or below C, M < 1, pointers not 16-byte aligned. */
+int ls_l2norm_scale(const uint16_t* x, int32_t ldx, int64_t M, int32_t C, const float* weight, uint16_t* y,
+                    int32_t ldy, void* stream);
+
+/* The tail of S3FDNet.forward and Detect.forward, one frame per block.  maps: a HOST array of
+ * the six head maps on the device, fp32 NHWC [n][h_l][w_l][c_l] with loc and conf side by side:
+ * c_0 = 4 + 4, c_l = 4 + 2 for l > 0; map_hw: a HOST array of the twelve sizes h_0, w_0, ...;
+ * priors fp32 [P][4] on the device (cx, cy, w, h; PriorBox.forward computed in float64 on the
+ * host), P = sum h_l w_l, level-major, row-major within a level.  Level 0's background logit is
+ * the maximum of its conf channels 0..2; two-class softmax; decode() with variances (0.1, 0.2)
+ * in the reference's operation order; the candidates are the scores > 0.05, of which exactly
+ * the 5000 highest enter the greedy NMS (descending score, area (x2 - x1)(y2 - y1), a box stays
+ * while IoU <= 0.3 with every kept one); out fp32 [n][750][5] = (score, x1, y1, x2, y2) in
+ * normalised coordinates, the first 750 kept boxes, zero rows after counts[f] (int32 [n]):
+ * the reference's output[:, 1].  keep_idx int32 [n][750] or NULL: the prior index of every kept
+ * box, -1 after the count.  Equal scores order towards the lower prior index.  The workspace
+ * (ls_s3fd_detect_workspace_bytes(n, P); 0 for sizes out of range) holds the sort keys and
+ * decoded boxes.  No allocation, no synchronisation, one launch.  LS_ERR_INVALID, nothing
+ * launched: null pointers, n outside 1..65535, P outside 1..65536 or not the maps' pixel
+ * count, priors not 16-byte aligned; LS_ERR_WORKSPACE: workspace null, misaligned or too
+ * small. */
+size_t ls_s3fd_detect_workspace_bytes(int32_t n, int32_t P);
+int ls_s3fd_detect(const float* const* maps, const int32_t* map_hw, int32_t n, const float* priors, int32_t P,
+                   float* out, int32_t* counts, int32_t* keep_idx, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
+/* The rest of S3FD.detect_faces: det fp32 [n][R][5] = (score, x1, y1, x2, y2) rows (ls_s3fd_detect's
+ * out, or the per-scale lists of a frame one after the other).  Per frame the rows with score >
+ * conf_th, in row order, times (frame_w, frame_h, frame_w, frame_h), then nms_ of box_utils.py:
+ * descending score, areas (x2 - x1)(y2 - y1), a box stays while inter / (area_i + area_j - inter)
+ * <= thresh against every kept one.  out fp32 [n][R][5] = (x1, y1, x2, y2, score) in nms_'s keep
+ * order, zero rows after counts[f]; keep_idx int32 [n][R] or NULL: each kept box's index in
+ * the frame's selected list, -1 after the count.  fp32 throughout (the reference runs nms_ in
+ * float64 on the same fp32 values).  One launch.  LS_ERR_INVALID, nothing launched: null
+ * pointers, n outside 1..65535, R outside 1..4096, a negative or NaN conf_th / thresh, a frame
+ * size that is not positive. */
+int ls_nms_boxes(const float* det, int32_t n, int32_t R, float conf_th, float frame_w, float frame_h, float thresh,
+                 float* out, int32_t* counts, int32_t* keep_idx, void* stream);
+
 int ls_abi_version(void);
 const char* ls_last_error(void);
 

@@ -173,6 +173,15 @@ _SIGS = {
     "ls_maxpool2d": (C.c_int, [c_vp] + [C.c_int32] * 11 + [c_vp, C.c_int32, c_vp]),
     "ls_sync_offset": (C.c_int, [c_vp, c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, c_vp, c_vp]),
     "ls_crop_track": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, c_vp, c_vp, c_vp]),
+    "ls_s3fd_prep": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, c_vp, c_vp]),
+    "ls_conv3x3_relu": (C.c_int, [c_vp] + [C.c_int32] * 5 + [c_vp, C.c_int32, c_vp, C.c_int32, c_vp, C.c_int32, c_vp]),
+    "ls_maxpool2x2_ceil": (C.c_int, [c_vp] + [C.c_int32] * 5 + [c_vp, C.c_int32, c_vp]),
+    "ls_l2norm_scale": (C.c_int, [c_vp, C.c_int32, C.c_int64, C.c_int32, c_vp, c_vp, C.c_int32, c_vp]),
+    "ls_s3fd_detect_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "ls_s3fd_detect": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, c_vp, C.c_int32, c_vp, c_vp,
+                                 c_vp, c_vp, C.c_size_t, c_vp]),
+    "ls_nms_boxes": (C.c_int, [c_vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, c_vp, c_vp,
+                               c_vp, c_vp]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -1049,3 +1049,122 @@ def crop_track(frames_u8, plan, out=None):
     assert tuple(out.shape) == (n, 224, 224, 3) and out.dtype == torch.uint8 and out.is_contiguous()
     check(lib.ls_crop_track(_p(frames_u8), n, H, W, _p(plan), _p(out), _stream()), "ls_crop_track")
     return out
+
+
+# ---- S3FD face detector (s3fd.py; csrc/ls_s3fd.hip) --------------------------------------
+
+
+def s3fd_prep_size(H, W, scale):
+    """cvRound(H s), cvRound(W s): round half to even, as Python's round() does on a float."""
+    return int(round(H * float(scale))), int(round(W * float(scale)))
+
+
+def s3fd_prep(frames_u8, scale, out=None):
+    """ls_s3fd_prep: frames uint8 (n, H, W, 3) RGB on the device -> bf16 (n, h, w, 8): resized by
+    ``scale`` as cv2.resize(., (0, 0), fx=s, fy=s) does, minus the means; channels R, G, B, 0.."""
+    lib = _lib.load()
+    n, H, W = _rgb_frames(frames_u8, "s3fd_prep")
+    s = float(scale)
+    if not 0.0 < s <= 1.0:
+        raise ValueError(f"s3fd_prep: the scale must be in (0, 1], got {scale}")
+    if s == 0.5:
+        raise ValueError("s3fd_prep: scale 0.5 is refused: cv2.resize switches to its 2 x 2 area path there, which "
+                         "ls_s3fd_prep does not restate")
+    h, w = s3fd_prep_size(H, W, s)
+    if h < 1 or w < 1:
+        raise ValueError(f"s3fd_prep: a {H} x {W} frame at scale {s} is empty")
+    if out is None:
+        out = torch.empty((n, h, w, 8), dtype=torch.bfloat16, device=frames_u8.device)
+    assert tuple(out.shape) == (n, h, w, 8) and out.dtype == torch.bfloat16 and out.is_contiguous()
+    check(lib.ls_s3fd_prep(_p(frames_u8), n, H, W, s, _p(out), _stream()), "ls_s3fd_prep")
+    return out
+
+
+def conv3x3_relu(x, pw: PackedGeneral, dilation=1, out=None):
+    """ls_conv3x3_relu: x (n, H, W, Cin) bf16 NHWC -> (n, H, W, N) bf16: 3 x 3, stride 1, padding =
+    dilation, bias, ReLU.  ``pw`` is the operand ls_conv_general takes for the same weight."""
+    lib = _lib.load()
+    n, H, W, Cin = x.shape
+    assert pw.window == (1, 3, 3) and pw.cin == Cin and pw.K == 9 * Cin and x.dtype == torch.bfloat16, \
+        (pw.window, pw.cin, Cin, pw.K, x.dtype)
+    if out is None:
+        out = torch.empty((n, H, W, pw.N), dtype=torch.bfloat16, device=x.device)
+    assert tuple(out.shape) == (n, H, W, pw.N) and out.dtype == torch.bfloat16
+    check(lib.ls_conv3x3_relu(_p(x), _ld(x), n, H, W, Cin, _p(pw.w), pw.N, _p(pw.bias), int(dilation), _p(out),
+                              _ld(out), _stream()), "ls_conv3x3_relu")
+    return out
+
+
+def maxpool2x2_ceil(x, out=None):
+    """ls_maxpool2x2_ceil: MaxPool2d(2, 2, ceil_mode=True) on bf16 NHWC."""
+    lib = _lib.load()
+    n, H, W, C_ = x.shape
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    if out is None:
+        out = torch.empty((n, Ho, Wo, C_), dtype=torch.bfloat16, device=x.device)
+    assert tuple(out.shape) == (n, Ho, Wo, C_) and out.dtype == x.dtype == torch.bfloat16
+    check(lib.ls_maxpool2x2_ceil(_p(x), _ld(x), n, H, W, C_, _p(out), _ld(out), _stream()), "ls_maxpool2x2_ceil")
+    return out
+
+
+def l2norm_scale(x, weight, out=None):
+    """ls_l2norm_scale: x (n, H, W, C) bf16 NHWC, weight fp32 (C,) -> L2Norm.forward, bf16."""
+    lib = _lib.load()
+    n, H, W, C_ = x.shape
+    assert x.dtype == torch.bfloat16 and weight.dtype == torch.float32 and tuple(weight.shape) == (C_,)
+    assert weight.is_contiguous()
+    if out is None:
+        out = torch.empty((n, H, W, C_), dtype=torch.bfloat16, device=x.device)
+    assert tuple(out.shape) == tuple(x.shape) and out.dtype == torch.bfloat16
+    check(lib.ls_l2norm_scale(_p(x), _ld(x), n * H * W, C_, _p(weight), _p(out), _ld(out), _stream()),
+          "ls_l2norm_scale")
+    return out
+
+
+S3FD_TOP_K = 750
+S3FD_MAX_PRIORS = 65536
+
+
+def s3fd_detect(maps, priors, want_idx=False):
+    """ls_s3fd_detect: the six head maps fp32 (n, h_l, w_l, 8 | 6) contiguous (loc | conf) and the
+    priors fp32 (P, 4), all on the device -> (out fp32 (n, 750, 5) = score, x1, y1, x2, y2,
+    counts int32 (n,)[, keep_idx int32 (n, 750)])."""
+    lib = _lib.load()
+    assert len(maps) == 6
+    n = maps[0].shape[0]
+    hw = []
+    for l, m in enumerate(maps):
+        assert m.dim() == 4 and m.shape[0] == n and m.shape[3] == (8 if l == 0 else 6), (l, tuple(m.shape))
+        assert m.dtype == torch.float32 and m.is_contiguous() and m.is_cuda
+        hw += [m.shape[1], m.shape[2]]
+    P = sum(hw[2 * l] * hw[2 * l + 1] for l in range(6))
+    if P > S3FD_MAX_PRIORS:
+        raise ValueError(f"s3fd_detect: {P} priors per frame exceed the kernel's {S3FD_MAX_PRIORS}: detect at a "
+                         "smaller scale")
+    assert tuple(priors.shape) == (P, 4) and priors.dtype == torch.float32 and priors.is_contiguous(), \
+        (tuple(priors.shape), P)
+    dev = maps[0].device
+    out = torch.empty((n, S3FD_TOP_K, 5), dtype=torch.float32, device=dev)
+    counts = torch.empty((n,), dtype=torch.int32, device=dev)
+    idx = torch.empty((n, S3FD_TOP_K), dtype=torch.int32, device=dev) if want_idx else None
+    nbytes = lib.ls_s3fd_detect_workspace_bytes(n, P)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    ptrs = (C.c_void_p * 6)(*[m.data_ptr() for m in maps])
+    sizes = (C.c_int32 * 12)(*hw)
+    check(lib.ls_s3fd_detect(ptrs, sizes, n, _p(priors), P, _p(out), _p(counts), _p(idx), _p(ws), nbytes, _stream()),
+          "ls_s3fd_detect")
+    return (out, counts, idx) if want_idx else (out, counts)
+
+
+def nms_boxes(det, conf_th, frame_w, frame_h, thresh=0.1, want_idx=False):
+    """ls_nms_boxes: det fp32 (n, R, 5) = score, x1, y1, x2, y2 -> (out fp32 (n, R, 5) = x1, y1, x2,
+    y2, score in frame coordinates and nms_'s keep order, counts int32 (n,)[, keep_idx])."""
+    lib = _lib.load()
+    assert det.dim() == 3 and det.shape[2] == 5 and det.dtype == torch.float32 and det.is_contiguous() and det.is_cuda
+    n, R = det.shape[:2]
+    out = torch.empty((n, R, 5), dtype=torch.float32, device=det.device)
+    counts = torch.empty((n,), dtype=torch.int32, device=det.device)
+    idx = torch.empty((n, R), dtype=torch.int32, device=det.device) if want_idx else None
+    check(lib.ls_nms_boxes(_p(det), n, R, float(conf_th), float(frame_w), float(frame_h), float(thresh), _p(out),
+                           _p(counts), _p(idx), _stream()), "ls_nms_boxes")
+    return (out, counts, idx) if want_idx else (out, counts)

@@ -559,10 +559,26 @@ class LipsyncPipeline:
         (eval/eval_sync_conf.py) on the frames about to be written: they are cropped about the
         boxes (synceval.crop_track) and evaluated against the request's audio (sync_evaluation).
         last_av_offset / last_lse_d / last_lse_c are set and an .npz output gains ``av_offset``,
-        ``lse_d`` and ``lse_c``; an .avi is unchanged."""
+        ``lse_d`` and ``lse_c``; an .avi is unchanged.
+        ``sync_eval=`` with ``face_detector=`` (an s3fd.S3FD on this device, or any object with
+        its ``detect(frames_u8, conf_th=, scale=)``) and no ``face_boxes=`` finds the boxes itself,
+        as eval_sync_conf.syncnet_eval does: the detector runs on the frames about to be
+        written, s3fd.track_faces builds the tracks (``face_track_args=`` overrides its
+        min_track=50 and the other thresholds) and every track is evaluated on its own crop and
+        its own stretch of the audio (sync_evaluation_tracks).  last_face_tracks is set too; no
+        track raises ValueError("Face not detected ...").  With both given, face_boxes wins."""
         from . import repeat as rep
         face_boxes = None
-        if kwargs.get("sync_eval") is not None:
+        detector = kwargs.get("face_detector") if kwargs.get("face_boxes") is None else None
+        if kwargs.get("sync_eval") is not None and detector is not None:
+            if not callable(getattr(detector, "detect", None)):
+                raise ValueError("face_detector= must have a detect(frames_u8, conf_th=, scale=) method (s3fd.S3FD)")
+            if kwargs.get("faces_only"):
+                raise ValueError("sync_eval with faces_only=True: the evaluation works on the restored frames and "
+                                 "the detector looks for faces in frame coordinates")
+            if abs(float(video_fps) - 25.0) > 1e-6:
+                raise ValueError(f"sync_eval: the evaluation is defined at 25 frames/s, not {video_fps}")
+        elif kwargs.get("sync_eval") is not None:
             if kwargs.get("face_boxes") is None:
                 raise ValueError("sync_eval= needs face_boxes=: the evaluation runs on a 224 x 224 crop track about "
                                  "the detector's boxes, and this build carries no face detector (a .npy path or an "
@@ -621,6 +637,9 @@ class LipsyncPipeline:
         if face_boxes is not None and rank0 and video_frames is None:
             raise ValueError(f"sync_eval: {video_path} yields no frames, so there are no restored frames to "
                              "evaluate (face_boxes are in frame coordinates)")
+        if kwargs.get("sync_eval") is not None and detector is not None and rank0 and video_frames is None:
+            raise ValueError(f"sync_eval: {video_path} yields no frames, so there are no restored frames to "
+                             "detect faces in")
         R = height or faces.shape[-1]
         self.check_inputs(R, width or R, callback_steps)
         # faces stored at another resolution are resized to R in run_windows, as the
@@ -680,6 +699,9 @@ class LipsyncPipeline:
         gate = None
         if face_boxes is not None:
             gate = self.sync_evaluation(kwargs["sync_eval"], frames_out, face_boxes[:n_out], audio_path, video_fps)
+        elif kwargs.get("sync_eval") is not None and detector is not None:
+            gate = self.sync_evaluation_tracks(kwargs["sync_eval"], detector, frames_out, audio_path, video_fps,
+                                               **(kwargs.get("face_track_args") or {}))
         if video_out_path.endswith(".avi"):
             # a playable file: Motion-JPEG encoded on the device + PCM audio (video.py).  An
             # AVI has no side channel for padding_duration, so the reference's trim of the
@@ -750,4 +772,44 @@ class LipsyncPipeline:
         wav = wav[:want] if wav.numel() >= want else torch.cat([wav, torch.zeros(want - wav.numel())])
         track = se.crop_track(frames_u8.to(net.device).contiguous(), face_boxes)
         self.last_av_offset, self.last_lse_d, self.last_lse_c = net.evaluate(frames=track, audio=wav)
+        return self.last_av_offset, self.last_lse_d, self.last_lse_c
+
+    def sync_evaluation_tracks(self, net, detector, frames_u8, audio_path, video_fps=25, conf_th=0.9, scale=0.25,
+                               **track_args):
+        """eval_sync_conf.syncnet_eval on a result: detect on the frames (SyncNetDetector.detect_face:
+        conf_th 0.9, scale 0.25), track (s3fd.track_faces, min_track=50 unless track_args says
+        otherwise; the clip is one shot), and evaluate every track on the crop of its own frame
+        range against the audio from frame0 / 25 to (frame_last + 1) / 25 s, as crop_video cuts
+        it.  av_offset = int(fmean(offsets)) and lse_c = fmean(confs) as the reference
+        aggregates them; lse_d = fmean of the tracks' min_dist, which the reference computes per
+        track and does not aggregate.  Sets last_av_offset, last_lse_d, last_lse_c and
+        last_face_tracks; no track raises ValueError("Face not detected ...")."""
+        from statistics import fmean
+
+        from . import s3fd
+        from . import synceval as se
+        from .audio import read_audio
+        if abs(float(video_fps) - 25.0) > 1e-6:
+            raise ValueError(f"sync_eval: the evaluation is defined at 25 frames/s, not {video_fps}")
+        frames = frames_u8.to(net.device).contiguous()
+        n = frames.shape[0]
+        dets = detector.detect(frames, conf_th=conf_th, scale=scale)
+        if len(dets) != n:
+            raise ValueError(f"face_detector: {len(dets)} detection lists for {n} frames")
+        track_args.setdefault("min_track", 50)
+        tracks = s3fd.track_faces(s3fd.faces_from_detections(dets), **track_args)
+        self.last_face_tracks = tracks
+        if not tracks:
+            raise ValueError(f"Face not detected in the {n} frames about to be written")
+        wav = read_audio(audio_path, se.SAMPLE_RATE).float()
+        want = int(n / video_fps * se.SAMPLE_RATE)
+        wav = wav[:want] if wav.numel() >= want else torch.cat([wav, torch.zeros(want - wav.numel())])
+        offsets, dists, confs = [], [], []
+        for t in tracks:
+            f0, f1 = int(t["frame"][0]), int(t["frame"][-1]) + 1
+            crop = se.crop_track(frames[f0:f1], t["bbox"])
+            a0, a1 = int(round(f0 / 25.0 * se.SAMPLE_RATE)), int(round(f1 / 25.0 * se.SAMPLE_RATE))
+            off, dist, conf = net.evaluate(frames=crop, audio=wav[a0:a1])
+            offsets.append(off), dists.append(dist), confs.append(conf)
+        self.last_av_offset, self.last_lse_d, self.last_lse_c = int(fmean(offsets)), fmean(dists), fmean(confs)
         return self.last_av_offset, self.last_lse_d, self.last_lse_c

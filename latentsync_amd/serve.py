@@ -115,6 +115,13 @@ def run_job(pipeline, payload: dict, data_dir: str, results_dir: str, resolution
     net = getattr(pipeline, "syncnet", None)
     if net is not None:
         kw["syncnet"] = net
+    # a worker started with LATENTSYNC_SYNCEVAL_CKPT and LATENTSYNC_S3FD_CKPT carries the classic
+    # SyncNet and the S3FD detector: the reference's quality gate runs on the result and the
+    # reply gains "av_offset", "lse_d" and "lse_c"
+    gate_net, gate_det = getattr(pipeline, "sync_eval", None), getattr(pipeline, "face_detector", None)
+    gate = gate_net is not None and gate_det is not None
+    if gate:
+        kw["sync_eval"], kw["face_detector"] = gate_net, gate_det
     # api.py:164-174: a dynamic clip with a text gets a GIF thumbnail (duration 6, fps 3, the
     # pipeline's defaults) with the text as its subtitle
     gif_path = None
@@ -135,6 +142,9 @@ def run_job(pipeline, payload: dict, data_dir: str, results_dir: str, resolution
              "elapsed_time": time.time() - start, "request_uuid": str(uuid.uuid4())}
     if net is not None:
         reply["sync_conf"] = float(pipeline.last_sync_conf)
+    if gate:
+        reply["av_offset"] = int(pipeline.last_av_offset)
+        reply["lse_d"], reply["lse_c"] = float(pipeline.last_lse_d), float(pipeline.last_lse_c)
     return reply
 
 
@@ -432,6 +442,13 @@ def default_pipeline(rank):
         scfg = load_config(os.environ.get("LATENTSYNC_SYNCNET_CONFIG", "configs/syncnet/syncnet_16_pixel_attn.yaml"))
         pipe.syncnet = StableSyncNet.from_pretrained(scfg["model"], os.environ["LATENTSYNC_SYNCNET_CKPT"], device=dev)
         pipe.syncnet.resolution = (scfg.get("data") or {}).get("resolution")
+    if os.environ.get("LATENTSYNC_SYNCEVAL_CKPT") and os.environ.get("LATENTSYNC_S3FD_CKPT"):
+        # opt-in quality gate: run_job passes both on and reports last_av_offset / last_lse_d / last_lse_c
+        from .s3fd import S3FD
+        from .synceval import SyncNetEval
+        pipe.sync_eval = SyncNetEval(device=dev)
+        pipe.sync_eval.loadParameters(os.environ["LATENTSYNC_SYNCEVAL_CKPT"])
+        pipe.face_detector = S3FD(device=dev, weights=os.environ["LATENTSYNC_S3FD_CKPT"])
     return pipe
 
 
