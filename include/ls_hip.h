@@ -282,7 +282,8 @@ int ls_attention(const ls_attn_desc* d, void* stream);
  * with one e8m0 scale per (head dim, 128-key tile) -- block scaling, the tile's max
  * mapped into [128, 256), the same scale for all four 32-key MX blocks of a tile; P (<= 2^8 by the kernel's rescale threshold) uses scale 1 and the
  * row sums come from the same e4m3 P.  Two launches (quantise, attend), capturable.
- * head_dim 40 or 80 (the UNet's 64^2 / 32^2 levels); q/k/v rows 16-B aligned, o rows 8-B aligned.
+ * head_dim 40 or 80 (the UNet's 64^2 / 32^2 levels); q/k/v rows 16-B aligned, o rows 8-B aligned
+ * (o and every o stride a multiple of 4 elements: the kernel stores 8 bytes at a time).
  * Workspace: ls_attention_fp8_workspace_bytes(d) (0 = unsupported head_dim), 16-B aligned;
  * its layout is documented in ls_attn.hip (the tests read it back).
  */

@@ -1654,8 +1654,10 @@ extern "C" int ls_attention_fp8(const ls_attn_desc* d, void* workspace, size_t w
   const bool aligned = d->q_si % 8 == 0 && d->k_si % 8 == 0 && d->v_si % 8 == 0 && d->q_sh % 8 == 0 &&
                        d->k_sh % 8 == 0 && d->v_sh % 8 == 0 && d->q_sb1 % 8 == 0 && d->q_sb2 % 8 == 0 &&
                        d->k_sb1 % 8 == 0 && d->k_sb2 % 8 == 0 && d->v_sb1 % 8 == 0 && d->v_sb2 % 8 == 0 &&
-                       (((uintptr_t)d->q | (uintptr_t)d->k | (uintptr_t)d->v) & 15) == 0 && d->o_si % 2 == 0 &&
-                       d->o_sh % 2 == 0 && d->o_sb1 % 2 == 0 && d->o_sb2 % 2 == 0 && ((uintptr_t)d->o & 7) == 0;
+                       (((uintptr_t)d->q | (uintptr_t)d->k | (uintptr_t)d->v) & 15) == 0 && d->o_si % 4 == 0 &&
+                       d->o_sh % 4 == 0 && d->o_sb1 % 4 == 0 && d->o_sb2 % 4 == 0 && ((uintptr_t)d->o & 7) == 0;
+  // attn8_kernel stores uint2 at orow + d (d a multiple of 4): every stride a multiple of 4 elements keeps
+  // each 8-byte store naturally aligned, as launch_attnw512's check does for the same store width
   if (!aligned) return fail(LS_ERR_INVALID, "ls_attention_fp8: q/k/v rows must be 16-B aligned, o rows 8-B");
   if (((long)d->nk + 128) * d->k_si * 2 >= (1L << 31)) return fail(LS_ERR_INVALID, "ls_attention_fp8: key set too long");
   const size_t need = ls_attention_fp8_workspace_bytes(d);

@@ -162,6 +162,98 @@ def attn_bound(q, k, v, scale, q_prescaled=False, q_err=None, k_err=None, v_err=
     return ref, _slack(b)
 
 
+U_E4M3 = 2.0 ** -4             # e4m3 keeps 3 fraction bits: round-to-nearest is within 2^-4 relative
+FP8_KT = 128                   # keys per tile of attn8_kernel / vt8_quant_kernel
+
+
+def fp8_scale_exponent(v):
+    """The exponent e = e8 - 127 of vt8_quant_kernel's e8m0 scale, per 128-key tile and head-dim
+    column: v (..., nk, d) -> (..., ceil(nk / 128), d) int64.  ls_attn.hip: "ex = (int)((
+    __float_as_uint(amax) >> 23) & 0xff) - 127", "e = amax > 0.f ? ex - 7 : -127", "e8 = max(0,
+    min(254, e + 127))", amax over the tile's 128 keys (the 32 of a thread, then the two xor
+    shuffles over the row's four lane groups; keys past nk are zeros)."""
+    v = f64(v)
+    nk, d = v.shape[-2:]
+    nt = -(-nk // FP8_KT)
+    vp = torch.zeros(v.shape[:-2] + (nt * FP8_KT, d), dtype=torch.float64)
+    vp[..., :nk, :] = v.abs()
+    amax = vp.reshape(v.shape[:-2] + (nt, FP8_KT, d)).amax(-2)
+    _, ex = torch.frexp(amax)  # amax = f 2^ex, f in [0.5, 1): floor(log2 amax) = ex - 1
+    e = torch.where(amax > 0, ex.to(torch.int64) - 1 - 7, torch.full_like(ex, -127, dtype=torch.int64))
+    return (e + 127).clamp(0, 254) - 127
+
+
+def attn_fp8_bound(q, k, v, scale, parts=False):
+    """(ref, B) in fp64 for o = softmax(scale q k^T) v of ls_attention_fp8 (vt8_quant_kernel +
+    attn8_kernel, ls_attn.hip); q (..., nq, d), k / v (..., nk, d) bf16-rounded.  With eps = 2^-4
+    (e4m3's unit roundoff), w the softmax weights and o = ref:
+
+        B = 2^-8 |o|
+          + (2 eps / (1 - eps)) sum_j w_j |v_j - o|
+          + (2 expm1(delta) + (nk + 6) 2^-23) sum_j w_j |v_j|
+          + (1 + 2 eps / (1 - eps)) (sum_j w_j b_v,j + 2^-16 sum_{j: w_j < 2^-11 max w} |v_j - o|)
+
+      * 2^-8 |o|: "w.x = pack2(oacc[g][nd][0] * inv, ...)", the one rounding to bf16.
+      * p to e4m3: "pk[g][4 * hf + f] = __builtin_amdgcn_cvt_pk_fp8_f32(fast_exp2(s[g][f][2]), ...)"
+        rounds every p to 3 fraction bits, p^ = p (1 + e), |e| <= eps in e4m3's normal range.
+        Row D of V^T is the constant 1.0 ("d == D ? 0x38383838u : 0u"), so "lt = __shfl(oacc[g][NDL]
+        [RL], ...)" is the sum of the SAME p^ the numerator uses: the weights the kernel applies are
+        w^_j = p^_j / sum p^, each within a factor (1 +- eps) / (1 -+ eps) of w_j, and sum w^ =
+        sum w = 1, so sum (w^_j - w_j) v_j = sum (w^_j - w_j)(v_j - o): the term is centred on o
+        and nearly vanishes on a row one key dominates.
+      * delta, in natural-log units, the error of a score:
+            delta = ((d + 2) 2^-23 + 2^-8) max_j scale sum_d |q_d| |k_jd|
+                  + (d + 2) 2^-23 (max_j |s_j| + 8 ln 2)
+        The first line is attn_bound's delta with q_prescaled=True ("f[e] *= c2; qf[g][kc] = ...
+        pack8(f)": Q times scale log2(e), rounded to bf16 again).  The second line (an extension,
+        read from "s[g][f] = ...mfma_f32_16x16x32_bf16(kf, qf[g][kc], kc == 0 ? negm[g] : s[g][f]"):
+        the accumulation chain starts at -m, so its partial sums are as large as |m| + sum |q k|, and
+        the integer m is within 8 of a score of the row ("dlt = need ? ceilf(mt[g]) - 7.f", taken
+        again whenever "mt[g] > TAU").  It is 10^-4 of the first.  A score error e moves p_j by
+        e^(+-e) in numerator and row sum alike.
+      * (nk + 6) 2^-23: nk accumulations each of numerator and row sum in the MFMA's fp32
+        accumulator (p^ times an e4m3 code times a power of two is exact), "1.f / lt" and the
+        product with it; the rescale "oacc[g][i] *= alpha" is the same factor on numerator and sum.
+      * b_v,j = max(eps |v_j|, 2^(e - 10)), e = fp8_scale_exponent: "cvt_pk_fp8_f32(v[4 * f] * inv_s,
+        ...)" rounds v 2^-e (the tile's row maximum in [128, 256), under e4m3's 448) to nearest:
+        2^-4 relative on normal codes, half the 2^-9 subnormal step below 2^-6.  The kernel's
+        weights multiply it: sum w^_j b_v,j <= (1 + 2 eps / (1 - eps)) sum w_j b_v,j.
+      * subnormal p: under the m in force a half's largest p is at most 2^8 and the row's largest
+        was in (2^6, 2^7] when m last moved, so the row sum is at least 2^6 (1 - eps); a p below
+        2^-6 lands on e4m3's 2^-9 grid, off by up to 2^-10 absolute, i.e. 2^-16 / (1 - eps) of the
+        row sum -- a later rescale shrinks both alike.  Such a key has w_j < 2^-12 max w; the set is
+        taken at 2^-11 to cover the score error.  With e_j the absolute errors, numerator - o * sum
+        = sum e_j (v_j - o), hence |v_j - o| (restated from |v_j|: the row sum carries e_j too).
+    The usual (1 + 2^-6), + 2^-126 slack.  parts=True also returns the terms by name (before the
+    slack): round, pquant, score, vquant, sub."""
+    q, k, v = f64(q), f64(k), f64(v)
+    d, nk = q.shape[-1], k.shape[-2]
+    s = scale * (q @ k.transpose(-1, -2))
+    w = torch.softmax(s, dim=-1)
+    ref = w @ v
+    smag = scale * (q.abs() @ k.abs().transpose(-1, -2))
+    delta = ((d + 2) * E_F32 + U_BF16) * smag.amax(-1, keepdim=True) \
+        + (d + 2) * E_F32 * (s.abs().amax(-1, keepdim=True) + 8 * math.log(2.0))
+    e = fp8_scale_exponent(v).repeat_interleave(FP8_KT, dim=-2)[..., :nk, :]
+    b_v = torch.maximum(U_E4M3 * v.abs(), torch.pow(2.0, e.to(torch.float64) - 10))
+    sub = (w < 2.0 ** -11 * w.amax(-1, keepdim=True)).to(torch.float64)
+    # sum_j w_ij |v_jd - o_id| and the subnormal keys' sum_j |v_jd - o_id|, one leading index at a time
+    lead = ref.shape[:-2]
+    wf, sf, vf, of = (t.reshape((-1,) + t.shape[-2:]) for t in (w, sub, v, ref))
+    cen, csub = torch.empty_like(of), torch.empty_like(of)
+    for i in range(of.shape[0]):
+        dev = (vf[i][None, :, :] - of[i][:, None, :]).abs()  # (nq, nk, d)
+        cen[i] = (wf[i][:, :, None] * dev).sum(1)
+        csub[i] = (sf[i][:, :, None] * dev).sum(1)
+    cen, csub = cen.reshape(lead + cen.shape[-2:]), csub.reshape(lead + csub.shape[-2:])
+    g = 2 * U_E4M3 / (1 - U_E4M3)
+    t = dict(round=U_BF16 * ref.abs(), pquant=g * cen,
+             score=(2 * torch.expm1(delta) + (nk + 6) * E_F32) * (w @ v.abs()),
+             vquant=(1 + g) * (w @ b_v), sub=(1 + g) * 2.0 ** -16 * csub)
+    b = _slack(t["round"] + t["pquant"] + t["score"] + t["vquant"] + t["sub"])
+    return (ref, b, t) if parts else (ref, b)
+
+
 def elem_bound(ref, term_mag, out_dtype):
     """Elementwise kernels (ls_elem.hip): 2^-8 |ref| (1 + 2^-6) for the bf16 rounding, plus
     16 2^-24 term_mag for the fp32 evaluation (at most 8 operations in any rounding mode on
@@ -784,22 +876,66 @@ def needle_keys(nk):
     return sorted({j for j in NEEDLE_KEYS + (nk - 2, nk - 1) if 0 <= j < nk})
 
 
-def needle_qkv(batch, heads, nq, nk, d, seed):
+def needle_qkv(batch, heads, nq, nk, d, seed, keys=None):
     """bf16-rounded q (batch, heads, nq, d), k, v (batch, heads, nk, d), random, with query row
     i (i < number of needle keys, i < nq) rewritten to 8 sqrt(d) k_j / |k_j|^2 for needle key j:
     at scale 1 / sqrt(d) its score on key j is 8, so that tile-boundary key carries most of
-    the row's weight."""
+    the row's weight.  keys: the needle keys (default needle_keys(nk))."""
     g = torch.Generator().manual_seed(seed)
     q = torch.randn(batch, heads, nq, d, generator=g)
     k = torch.randn(batch, heads, nk, d, generator=g)
     v = torch.randn(batch, heads, nk, d, generator=g)
     k = bf16_round(k)
-    for i, j in enumerate(needle_keys(nk)):
+    for i, j in enumerate(needle_keys(nk) if keys is None else keys):
         if i >= nq:
             break
         kj = k[:, :, j]
         q[:, :, i] = 8.0 * math.sqrt(d) * kj / (kj * kj).sum(-1, keepdim=True)
     return bf16_round(q), k, bf16_round(v)
+
+
+# ---------------------------------------------------------------- fp8 attention cases
+# (tests/test_gpu_edges_fp8.py runs them; tests/test_parity_bounds.py walks each on the CPU)
+# attn8_kernel: 128 queries per block (4 waves x QG 2 x 16), 128-key tiles in two 64-key halves,
+# an LDS ring of depth 2.  (nq, nk, batch, heads):
+FP8_SHAPES = (
+    (1, 1, 2, 2),      # one key
+    (17, 77, 2, 2),    # a single partial tile, its second half partly masked
+    (33, 64, 2, 2),    # the second half entirely masked
+    (130, 128, 2, 2),  # exactly one full tile, no partial one; two query blocks, the second of 2 rows
+    (130, 129, 2, 2),  # one key in the partial tile
+    (70, 257, 2, 2),   # three tiles: the ring's slot is reused
+    (129, 385, 2, 2),  # four tiles
+    (65, 300, 1, 3),   # a grid of 3 blocks: attn_xcd_remap's remainder branch
+)
+FP8_CASES = tuple((f"d{d}_{nq}x{nk}_{kind}", d, batch, heads, nq, nk, kind)
+                  for d in (40, 80) for nq, nk, batch, heads in FP8_SHAPES for kind in ("needle", "random6"))
+# keys that separate the three fields of the permutation 16 (j >> 2) + 4 lg + (j & 3)
+FP8_PERM_KEYS = (3, 4, 12, 20, 67, 191, 192, 256)
+
+
+def fp8_needle_keys(nk):
+    return sorted({j for j in NEEDLE_KEYS + FP8_PERM_KEYS + (nk - 2, nk - 1) if 0 <= j < nk})
+
+
+def fp8_qkv(d, batch, heads, nq, nk, kind, seed=37):
+    """bf16-rounded q (batch, heads, nq, d), k, v (batch, heads, nk, d) of an fp8 case.
+    "needle": needle_qkv on fp8_needle_keys, V times a power of two in 2^-6 .. 2^6 per (batch,
+    head, key), so a scale byte from another row or tile shows.  "random6": Gaussian, Q times 6:
+    scores of deviation 6 (8.7 in log2 units), so the running m moves often and by little.
+    (The seed is one at which the one-key cases have a row with a score below -4 at d 40 and 80:
+    tests/test_parity_bounds.py asserts that, and its coverage conditions, from the inputs.)"""
+    seed = 100000 * seed + 1000 * nq + 10 * nk + d
+    if kind == "needle":
+        q, k, v = needle_qkv(batch, heads, nq, nk, d, seed, keys=fp8_needle_keys(nk))
+        g = torch.Generator().manual_seed(seed + 1)
+        return q, k, v * torch.pow(2.0, torch.randint(-6, 7, (batch, heads, nk, 1), generator=g).float())
+    if kind != "random6":
+        raise ValueError(kind)
+    g = torch.Generator().manual_seed(seed)
+    r = lambda n: bf16_round(torch.randn(batch, heads, n, d, generator=g))
+    q, k, v = r(nq), r(nk), r(nk)
+    return bf16_round(6.0 * q), k, v
 
 
 # ---------------------------------------------------------------- norm cases (tests/test_gpu_edges_norm.py)

@@ -5,7 +5,9 @@ arithmetic (bf16 inputs, fp32 accumulation, round-to-nearest-even to bf16; for a
 also exp2, P rounded to bf16 and an fp32 row sum) must PASS the derived bound, and planted
 defects of the kind tiled kernels really have must be REJECTED by it -- while the old
 whole-output Frobenius ratio (conftest.rel_err < 1e-2) lets the GEMM defects through, which
-is kept on record here."""
+is kept on record here.  The fp8 attention (ls_attention_fp8) has its own restatement at the end: a
+walk of the keys in attn8_kernel's tile order, which must pass attn_fp8_bound on every case of the
+GPU file, and seven planted defects that must leave it."""
 import math
 
 import pytest
@@ -14,6 +16,7 @@ import torch.nn.functional as F
 
 import parity as P
 from conftest import rel_err
+from oracle import fp8_cpu as Q8
 
 LOG2E = 1.4426950408889634
 
@@ -1098,3 +1101,314 @@ def test_rb_chunk_counts(M, N, K, fm, chunks):
         lib.ls_set_tuning(15, 1)
     assert plan["family"] == 1 and plan["rb_fm"] == fm and plan["rb_flags"] == 0, plan
     assert P.rb_chunk_counts(plan, N, M) == chunks
+
+
+# ---------------------------------------------------------------- fp8 attention (ls_attention_fp8)
+def emulate_attn_fp8_tiled(q, k, v, scale, **defect):
+    """attn8_kernel's key walk for one (batch, head): q (nq, d), k / v (nk, d) bf16 values ->
+    (o fp32 (nq, d), not yet rounded to bf16, trace).  oracle.fp8_cpu.attention_fp8 takes the row
+    maximum in one pass; this restatement moves m as the kernel does:
+      * 128-key tiles in two 64-key halves; the keys past nk of the partial tile are -inf (their K
+        rows are the buffer load's zeros, their V codes zero, the sum row 1.0 all the same);
+      * the first half sets m = ceil(half max) - 7; afterwards m moves by dlt = ceil(half max - m)
+        - 7 whenever a half's maximum exceeds m + 8 ("need = first || mt[g] > TAU");
+      * a move multiplies the accumulators, the sum column included, by 2^-dlt; when any row of a
+        wave (32 rows: QG 2 x 16) moves in a tile's second half, the wave's first-half P, packed
+        against the old m, is accumulated on its own first ("pv(pk)" with the second half zeroed);
+      * p = e4m3(2^(s - m)), accumulated against the dequantised V^T and its constant row D.
+    trace: moved (nq, tiles, 2) bool and dlt (nq, tiles, 2), per (tile, half).
+
+    Planted defects (keywords): drop_key=j (its score -inf), sum_without=j (row D of V^T zero at
+    key j), unmask=j (a key past nk not masked), skip_rescale (alpha = 1 on a move in a later
+    tile), skip_flush (no separate accumulation of the first half), scale_off=(tile, lg) (that lane
+    group's 32 keys dequantised with a scale byte one too high), swap_keys=(j1, j2) (their V^T
+    columns exchanged)."""
+    nq, D = q.shape
+    nk = k.shape[0]
+    nt = -(-nk // Q8.KT)
+    qs = P.bf16_round(q.float() * (scale * LOG2E))
+    kp = torch.zeros(nt * Q8.KT, D)
+    kp[:nk] = k.float()
+    codes, e8 = Q8.quant_vt(v)
+    vq = Q8.dequant_vt(codes, e8, nt * Q8.KT)
+    if "scale_off" in defect:
+        t, lg = defect["scale_off"]
+        vq[t * Q8.KT + Q8.key_perm()[32 * lg:32 * lg + 32]] *= 2.0
+    if "swap_keys" in defect:
+        j1, j2 = defect["swap_keys"]
+        vq[[j1, j2]] = vq[[j2, j1]]
+    va = torch.cat([vq, torch.ones(nt * Q8.KT, 1)], 1)
+    if "sum_without" in defect:
+        va[defect["sum_without"], D] = 0.0
+    s_all = qs @ kp.t()
+    if "drop_key" in defect:
+        s_all[:, defect["drop_key"]] = -float("inf")
+    valid = torch.arange(nt * Q8.KT) < nk
+    if "unmask" in defect:
+        valid[defect["unmask"]] = True
+    wave = torch.arange(nq) // 32
+    m = torch.zeros(nq)
+    acc = torch.zeros(nq, D + 1)
+    moved = torch.zeros(nq, nt, 2, dtype=torch.bool)
+    dlts = torch.zeros(nq, nt, 2)
+    for t in range(nt):
+        pend = torch.zeros(nq, 64)
+        for hf in range(2):
+            k0 = t * Q8.KT + 64 * hf
+            s = s_all[:, k0:k0 + 64] - m[:, None]
+            s = torch.where(valid[k0:k0 + 64], s, torch.full_like(s, -float("inf")))
+            mt = s.amax(-1)
+            first = t == 0 and hf == 0
+            need = torch.ones(nq, dtype=torch.bool) if first else mt > 8.0
+            again = (torch.zeros(int(wave[-1]) + 1).index_add_(0, wave, need.float()) > 0)[wave]
+            if hf == 1 and not defect.get("skip_flush"):
+                acc[again] += pend[again] @ va[k0 - 64:k0]
+                pend[again] = 0.0
+            dlt = torch.where(need, torch.ceil(mt) - 7.0, torch.zeros(nq))
+            alpha = torch.zeros(nq) if first else torch.exp2(-dlt)
+            if defect.get("skip_rescale") and t > 0:
+                alpha = torch.ones(nq)
+            m = m + dlt
+            s = s - dlt[:, None]
+            acc = acc * alpha[:, None]
+            moved[:, t, hf], dlts[:, t, hf] = need, dlt
+            p = torch.exp2(s).to(torch.float8_e4m3fn).float()
+            if hf == 0:
+                pend = p
+            else:
+                acc += torch.cat([pend, p], 1) @ va[k0 - 64:k0 + 64]
+    return acc[:, :D] / acc[:, D:], dict(moved=moved, dlt=dlts)
+
+
+_FP8 = {c[0]: c for c in P.FP8_CASES}
+_FP8_CACHE = {}
+
+
+def fp8_case(name):
+    """Inputs, fp64 reference, bound and the clean tile-order emulation (per pair, with its trace)
+    of one case of P.FP8_CASES, computed once."""
+    if name not in _FP8_CACHE:
+        _, d, batch, heads, nq, nk, kind = _FP8[name]
+        q, k, v = P.fp8_qkv(d, batch, heads, nq, nk, kind)
+        scale = 1 / math.sqrt(d)
+        ref, bound, parts = P.attn_fp8_bound(q, k, v, scale, parts=True)
+        emu = [[emulate_attn_fp8_tiled(q[b, h], k[b, h], v[b, h], scale) for h in range(heads)] for b in range(batch)]
+        o = torch.stack([torch.stack([e[0] for e in row]) for row in emu])
+        w = torch.softmax(scale * (P.f64(q) @ P.f64(k).transpose(-1, -2)), -1)
+        _FP8_CACHE[name] = dict(q=q, k=k, v=v, scale=scale, ref=ref, bound=bound, parts=parts, o=o, w=w,
+                                trace=[[e[1] for e in row] for row in emu])
+    return _FP8_CACHE[name]
+
+
+@pytest.mark.parametrize("name", list(_FP8))
+def test_fp8_tiled_emulation_passes(name):
+    """The tile-order walk passes attn_fp8_bound, and agrees with the one-pass emulation
+    (oracle.fp8_cpu.attention_fp8, the same fp32 scores) within the bound's terms that are not a
+    normal-range quantisation: the fp32 / score term and twice the subnormal-p term (the two m
+    differ by 2^k, k in {0, 1}, so a p of the key set the term counts sits on a 2^-9 grid in one
+    walk and on a finer one in the other: each is within 2^-10 of the unrounded p)."""
+    c = fp8_case(name)
+    worst = P.assert_elementwise(bfr(c["o"]), c["ref"], c["bound"], where=dict(rows=16, cols=16), name=name)
+    q, k, v = c["q"], c["k"], c["v"]
+    one = torch.stack([torch.stack([Q8.attention_fp8(q[b, h], k[b, h], v[b, h], c["scale"]) for h in range(q.shape[1])])
+                       for b in range(q.shape[0])])
+    tol = c["parts"]["score"] + 2 * c["parts"]["sub"] + P.TINY
+    agree = P.assert_elementwise(c["o"], P.f64(one), tol, name=f"{name} tile-order vs one-pass")
+    print(f"fp8 emulation {name}: err/bound {worst:.3f}, tile-order vs one-pass {agree:.3f} of its tolerance")
+
+
+def test_fp8_cases_cover_the_running_max():
+    """Read from the emulation's trace and the fp64 weights alone: the case list holds rows whose m
+    moves in a second half, rows whose m moves in a later tile by at most 3 while the keys before
+    that half keep more than 1 % of the row's weight (so a missed rescale shows), rows whose m
+    never moves after the first half although there are more keys, and rows whose first m is negative."""
+    second = later = never = negative = 0
+    for name, d, batch, heads, nq, nk, kind in P.FP8_CASES:
+        c = fp8_case(name)
+        for b in range(batch):
+            for h in range(heads):
+                mv, dl = c["trace"][b][h]["moved"], c["trace"][b][h]["dlt"]
+                after = mv.clone()
+                after[:, 0, 0] = False
+                assert bool(mv[:, 0, 0].all()) and bool((dl[after] >= 2).all())  # a later move is by 2 at least
+                second += int(mv[:, :, 1].any(1).sum())
+                negative += int((dl[:, 0, 0] < 0).sum())
+                if nk > 64:
+                    never += int((~mv.reshape(nq, -1)[:, 1:].any(1)).sum())
+                before = torch.cumsum(c["w"][b, h], -1)
+                for t in range(1, mv.shape[1]):
+                    for hf in range(2):
+                        k0 = min(t * 128 + 64 * hf, nk)
+                        later += int((mv[:, t, hf] & (dl[:, t, hf] <= 3) & (before[:, k0 - 1] > 0.01)).sum())
+    print(f"fp8 coverage: {second} rows move in a second half, {later} small moves in a later tile, "
+          f"{never} rows never move again, {negative} rows start at a negative m")
+    assert second > 0 and later > 0 and never > 0 and negative > 0
+
+
+OLD_ROWS = 32768  # rows of the largest output tests/test_gpu_fp8.py takes its ratios over: (1, 4096, 4096, 8, 40)
+
+
+def fp8_defect_rows(name, candidates, what):
+    """Plant each (row, defect) of `candidates` into that one row of pair (0, 0) of the clean
+    emulation; returns [(row, err/bound of the row, rejected, rel vs emulation, rel vs fp64)].
+    The Frobenius ratios are taken over the case's whole output, as tests/test_gpu_fp8.py does."""
+    c = fp8_case(name)
+    clean = bfr(c["o"])
+    out = []
+    for row, defect in candidates:
+        bad, _ = emulate_attn_fp8_tiled(c["q"][0, 0], c["k"][0, 0], c["v"][0, 0], c["scale"], **defect)
+        got = clean.clone()
+        got[0, 0, row] = bfr(bad[row])
+        ratio = float(((P.f64(got) - c["ref"]).abs() / c["bound"])[0, 0, row].max())
+        try:
+            P.assert_elementwise(got, c["ref"], c["bound"], name=what)
+            rejected = False
+        except AssertionError as e:
+            assert f"(rows [{row}])" in str(e), str(e)  # pair (0, 0)'s row: the only one outside
+            rejected = True
+        assert rejected == (ratio > 1.0)
+        out.append((row, ratio, rejected, rel_err(got, clean), rel_err(got, c["ref"])))
+        print(f"{name} {what} {defect} in row {row}: err/bound {ratio:.2f}, Frobenius vs emulation {out[-1][3]:.2e}, "
+              f"vs fp64 {out[-1][4]:.2e}")
+    return out
+
+
+def fp8_old_check_blind(name, res):
+    """What tests/test_gpu_fp8.py asserts of an output -- rel_err < 6e-2 against the fp64 softmax
+    and < 4e-3 against the emulation -- for the rejected one-row defects of `res`: at least one of
+    them stays under both.  The ratio against fp64 is taken over the case's output as it is.  The
+    one against the emulation cannot be: a case here has 4 to 520 rows, and a row that leaves a
+    bound about 13 % of itself wide weighs at least 0.13 / sqrt(520) = 5.7e-3 in such an output.
+    The outputs of that file have 3200 to 32768 rows, and one wrong row among R error-free ones of
+    like size weighs 1 / sqrt(R): the measured ratio is taken times sqrt(rows / OLD_ROWS), what the
+    same row weighs in the largest output that file checks."""
+    _, d, batch, heads, nq, nk, kind = _FP8[name]
+    shrink = math.sqrt(batch * heads * nq / OLD_ROWS)
+    hidden = [(r, e * shrink, f) for r, _, rej, e, f in res if rej and e * shrink < 4e-3 and f < 6e-2]
+    print(f"{name}: the Frobenius check lets through the defect in rows {[r for r, _, _ in hidden]}")
+    assert hidden, res
+
+
+def _needle_rows(name):
+    """(row, key, strong) of pair (0, 0)'s needle rows whose key carries most of the row's weight.
+    strong: w_j |v_j| is, in some column, above 4 times what all the other keys together bring
+    (sum_i w_i |v_i|).  V spans 2^-6 .. 2^6 per key, so under a small needle the other keys' few
+    per cent of the weight make most of the row and of its bound: a defect in the needle's VALUE
+    must show on the strong rows, and may hide on the others."""
+    c = fp8_case(name)
+    _, d, batch, heads, nq, nk, kind = _FP8[name]
+    w, v = c["w"][0, 0], P.f64(c["v"][0, 0])
+    rows = []
+    for i, j in enumerate(P.fp8_needle_keys(nk)[:nq]):
+        own = w[i, j] * v[j].abs()
+        rest = w[i] @ v.abs() - own
+        if float(w[i, j]) > 0.5:
+            rows.append((i, j, float(own.max()) > 4 * float(rest.max())))
+    assert rows
+    return rows
+
+
+FP8_NEEDLE_MUT = [n for n in _FP8 if n.endswith("needle") and _FP8[n][5] > 1]
+
+
+@pytest.mark.parametrize("name", FP8_NEEDLE_MUT)
+def test_fp8_dropped_needle_key_rejected(name):
+    res = fp8_defect_rows(name, [(i, dict(drop_key=j)) for i, j, _ in _needle_rows(name)], "dropped key")
+    assert all(rej and ratio > 3 for _, ratio, rej, _, _ in res), res
+    fp8_old_check_blind(name, res)
+
+
+@pytest.mark.parametrize("name", FP8_NEEDLE_MUT)
+def test_fp8_row_sum_missing_key_rejected(name):
+    res = fp8_defect_rows(name, [(i, dict(sum_without=j)) for i, j, _ in _needle_rows(name)], "row sum without key")
+    assert all(rej and ratio > 3 for _, ratio, rej, _, _ in res), res
+    fp8_old_check_blind(name, res)
+
+
+def _strong_rejected(name, cand, res):
+    strong = {i for i, _, st in _needle_rows(name) if st}
+    hit = [rej for (row, _), (_, _, rej, _, _) in zip(cand, res) if row in strong]
+    assert hit and all(hit), res
+    return len(hit)
+
+
+@pytest.mark.parametrize("name", FP8_NEEDLE_MUT)
+def test_fp8_scale_byte_off_by_one_rejected(name):
+    """The scale byte of the needle key's lane group (32 keys of its tile) one too high: rejected
+    on every strong needle row."""
+    perm = Q8.key_perm()
+    cand = [(i, dict(scale_off=(j // 128, int((perm == j % 128).nonzero()) // 32))) for i, j, _ in _needle_rows(name)]
+    res = fp8_defect_rows(name, cand, "scale byte + 1")
+    _strong_rejected(name, cand, res)
+    fp8_old_check_blind(name, res)
+
+
+@pytest.mark.parametrize("name", FP8_NEEDLE_MUT)
+def test_fp8_exchanged_keys_rejected(name):
+    """The needle key's V^T column exchanged with that of the key 4 further on (the next lane
+    group's, same j) or, at the tile's or the key set's end, 4 back: rejected on every strong
+    needle row."""
+    nk = _FP8[name][5]
+    cand = []
+    for i, j, _ in _needle_rows(name):
+        j2 = j + 4 if (j + 4) // 128 == j // 128 and j + 4 < nk else j - 4
+        if j2 >= 0:
+            cand.append((i, dict(swap_keys=(j, j2))))
+    res = fp8_defect_rows(name, cand, "exchanged keys")
+    _strong_rejected(name, cand, res)
+    fp8_old_check_blind(name, res)
+
+
+@pytest.mark.parametrize("d", [40, 80])
+def test_fp8_unmasked_key_rejected(d):
+    """Key nk = 1 of the one-key case left unmasked: its K row is the buffer load's zeros (score
+    0), its V codes are zero, the sum row is 1.0 there too.  The rows whose only score is below
+    -4 (in log2 units) lose most of their value to it."""
+    name = f"d{d}_1x1_random6"
+    c = fp8_case(name)
+    ok = False
+    for b in range(2):
+        for h in range(2):
+            s = float(P.bf16_round(c["q"][b, h] * (c["scale"] * LOG2E)) @ c["k"][b, h].t())
+            bad, _ = emulate_attn_fp8_tiled(c["q"][b, h], c["k"][b, h], c["v"][b, h], c["scale"], unmask=1)
+            ratio = float(((P.f64(bfr(bad)) - c["ref"][b, h]).abs() / c["bound"][b, h]).max())
+            print(f"{name} pair ({b}, {h}) score {s:.1f}: unmasked key 1, err/bound {ratio:.2f}")
+            if s < -4:
+                ok = True
+                with pytest.raises(AssertionError, match="err/bound"):
+                    P.assert_elementwise(bfr(bad), c["ref"][b, h], c["bound"][b, h])
+    assert ok
+
+
+def _moving_rows(name, second_half):
+    """Rows of pair (0, 0) whose m moves in a later tile (second_half False) or in a second half
+    (True) while the keys before that half keep more than 5 % of the row's weight."""
+    c = fp8_case(name)
+    nk = _FP8[name][5]
+    mv = c["trace"][0][0]["moved"]
+    before = torch.cumsum(c["w"][0, 0], -1)
+    rows = set()
+    for t in range(0 if second_half else 1, mv.shape[1]):
+        for hf in ((1,) if second_half else (0, 1)):
+            k0 = min(t * 128 + 64 * hf, nk)
+            rows |= set(torch.nonzero(mv[:, t, hf] & (before[:, k0 - 1] > 0.05)).reshape(-1).tolist())
+    return sorted(rows)
+
+
+@pytest.mark.parametrize("name", ["d40_70x257_random6", "d80_70x257_random6", "d40_129x385_random6", "d80_129x385_random6"])
+def test_fp8_skipped_rescale_rejected(name):
+    """alpha = 1 where m moves in a later tile: the earlier keys keep 2^dlt times their weight."""
+    rows = _moving_rows(name, False)
+    res = fp8_defect_rows(name, [(r, dict(skip_rescale=True)) for r in rows], "skipped rescale")
+    assert sum(rej for _, _, rej, _, _ in res) >= len(res) // 2 > 0, res
+    fp8_old_check_blind(name, res)
+
+
+@pytest.mark.parametrize("name", ["d40_130x128_random6", "d80_130x129_random6", "d40_129x385_random6", "d80_129x385_random6"])
+def test_fp8_skipped_first_half_flush_rejected(name):
+    """m moves in a tile's second half and the first half's P, packed against the old m, is
+    accumulated after the rescale instead of before it."""
+    rows = _moving_rows(name, True)
+    res = fp8_defect_rows(name, [(r, dict(skip_flush=True)) for r in rows], "skipped first-half flush")
+    assert sum(rej for _, _, rej, _, _ in res) >= len(res) // 2 > 0, res
+    fp8_old_check_blind(name, res)
