@@ -538,7 +538,9 @@ int ls_gemm_occupancy(int32_t which);
  * audio fp32 [n_samples] (16 kHz mono), filters fp32 [n_mels][201];
  * out bf16 [t_pad][n_mels] frame-major, T = n_samples / 160 frames, zero for
  * T <= t < t_pad (the transcribe segment pad, whisper/audio.py pad_or_trim).
- * Workspace: ls_log_mel_workspace_bytes. */
+ * Workspace: ls_log_mel_workspace_bytes = 256 + T * n_mels * 4: the clip maximum (one
+ * ordered uint32) at byte 0, the fp32 log10 mel rows [T][n_mels] before the floor at
+ * byte offset 256; it is rewritten by every call and may hold anything before one. */
 size_t ls_log_mel_workspace_bytes(int64_t n_samples, int32_t n_mels);
 int ls_log_mel(const float* audio, int64_t n_samples, const float* filters, int32_t n_mels, int64_t t_pad,
                uint16_t* out, void* workspace, size_t workspace_bytes, void* stream);

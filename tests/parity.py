@@ -1165,3 +1165,186 @@ def tattn_case(C, S, F, seed=0):
     bpe = beta.reshape(1, C).repeat(16, 1) + pe[:16]
     return dict(x=x, gamma=gamma, beta=beta, pe=pe, bpe=bpe, wq=wq, wk=wk, wv=wv, wqp=bf16_round(wq * sc),
                 wkr=bf16_round(wk), wvr=bf16_round(wv))
+
+
+# ---------------------------------------------------------------- Whisper log-mel (ls_audio.hip)
+MEL_NFFT, MEL_HOP, MEL_NFREQ, MEL_BLOCK = 400, 160, 201, 8  # MEL_BLOCK: frames per block of log_mel_kernel
+MEL_LOG_FLOOR = float(torch.tensor(1e-10, dtype=torch.float32))  # the kernel's 1e-10f
+
+
+def mel_frame_index(n, T):
+    """(T, 400) int64: the sample frame t reads at window position m, t 160 + m - 200 reflected
+    once at either end (torch.stft centre=True, pad_mode="reflect"; n > 200 keeps it in range)."""
+    j = torch.arange(T)[:, None] * MEL_HOP + torch.arange(MEL_NFFT)[None, :] - MEL_NFFT // 2
+    j = j.abs()
+    return torch.where(j >= n, 2 * (n - 1) - j, j)
+
+
+def log_mel_bound(wave, filters, t_pad):
+    """(l_ref, l_bound, v_ref, v_bound) in fp64 for ls_log_mel (log_mel_kernel + mel_norm_kernel,
+    ls_audio.hip): l (T, n_mels) the fp32 log-mel rows of the workspace, v (t_pad, n_mels) the bf16
+    output; wave (n,) fp32 samples, filters (n_mels, 201) fp32, T = n // 160.
+
+    Oracle: the exact STFT -- periodic Hann 400 (0.5 - 0.5 cos(2 pi m / 400)), hop 160, centre
+    reflect padding (mel_frame_index), X_k = sum_m x_m w_m e^(-2 pi i k m / 400) with the twiddle
+    index k m reduced mod 400 in integers, P_k = |X_k|^2, s_b = sum_k f_bk P_k, l = log10(max(s,
+    1e-10)); floor = max(l) - 8 over the whole clip, v = (max(l, floor) + 4) / 4, rows T .. t_pad
+    zero.
+
+    Bound, as an interval carried through the monotone steps:
+      * one DFT component.  With A_f = sum_m |x_m w_m| of the frame, re and im are each off by at
+        most E_f = (400 + 8) 2^-23 A_f: 400 sequential fp32 accumulations in any rounding (the
+        products may or may not be contracted), and 8 more units for what each term carries
+        before it is summed -- the sincospif table (cs[], sn[] within 2 ulp), the Hann value 0.5 -
+        0.5 cs[m] (a product and a subtraction of numbers <= 1), the product with the sample and
+        the product with the twiddle.
+      * P_k = re^2 + im^2: |dP_k| <= 2 (|re| + |im|) E_f + 2 E_f^2 + 3 2^-23 P_k (two squares and
+        the addition).
+      * s_b: the filter weights are non-negative, so ds_b = sum_k f_bk dP_k + 202 2^-23 s_b (201
+        products and additions of non-negative terms, any order).
+      * l in [log10(max(s - ds, 1e-10)), log10(max(s + ds, 1e-10))], widened by 4 2^-23 |l| for
+        log10f (2 ulp) and fmaxf's exactness; l_bound is the larger distance of l_ref to an end.
+      * the floor lies between the maxima of the two ends minus 8 (the kernel's maximum is the
+        maximum of values inside their intervals; ord_enc / atomicMax are exact), and
+        v = (max(l, floor) + 4) / 4 is monotone in l and in the floor, so its interval comes from
+        the two ends; then 3 2^-23 (|max(l, floor)| + 4) / 4 for the three fp32 operations (- 8,
+        + 4, / 4) and 2^-8 |v| for the round-to-nearest bf16 store (f2bf).  v_bound is the larger
+        distance of v_ref to an end.  The zero rows are exact (their bound is the 2^-126 of the
+        slack alone; the GPU test also compares their bits).
+    (1 + 2^-6) and + 2^-126 as everywhere."""
+    x = f64(wave).reshape(-1)
+    fb = f64(filters)
+    n = x.numel()
+    T = n // MEL_HOP
+    n_mels = fb.shape[0]
+    m = torch.arange(MEL_NFFT)
+    win = 0.5 - 0.5 * torch.cos(2.0 * math.pi * m.to(torch.float64) / MEL_NFFT)
+    xw = x[mel_frame_index(n, T)] * win  # (T, 400)
+    ph = 2.0 * math.pi * ((torch.arange(MEL_NFREQ)[:, None] * m[None, :]) % MEL_NFFT).to(torch.float64) / MEL_NFFT
+    re, im = xw @ torch.cos(ph).T, -(xw @ torch.sin(ph).T)  # (T, 201)
+    pw = re * re + im * im
+    E = (MEL_NFFT + 8) * E_F32 * xw.abs().sum(1, keepdim=True)
+    dP = 2 * (re.abs() + im.abs()) * E + 2 * E * E + 3 * E_F32 * pw
+    s = pw @ fb.T
+    ds = dP @ fb.T + (MEL_NFREQ + 1) * E_F32 * s
+    log = lambda t: torch.log10(t.clamp_min(MEL_LOG_FLOOR))
+    l_ref, lo, hi = log(s), log(s - ds), log(s + ds)
+    lo, hi = lo - 4 * E_F32 * lo.abs(), hi + 4 * E_F32 * hi.abs()
+    l_bound = _slack(torch.maximum(hi - l_ref, l_ref - lo))
+    lo, hi = l_ref - l_bound, l_ref + l_bound  # the slack carried on
+    norm = lambda l, fl: (torch.maximum(l, fl) + 4.0) / 4.0
+    f_ref, f_lo, f_hi = l_ref.max() - 8.0, lo.max() - 8.0, hi.max() - 8.0
+    f_lo, f_hi = f_lo - E_F32 * f_lo.abs(), f_hi + E_F32 * f_hi.abs()
+    v, v_lo, v_hi = norm(l_ref, f_ref), norm(lo, f_lo), norm(hi, f_hi)
+    ops3 = 3 * E_F32 * (torch.maximum(torch.maximum(lo, f_lo).abs(), torch.maximum(hi, f_hi).abs()) + 4.0) / 4.0
+    b = torch.maximum(v_hi - v, v - v_lo) + ops3 + U_BF16 * torch.maximum(v_lo.abs(), v_hi.abs())
+    v_ref = torch.zeros(t_pad, n_mels, dtype=torch.float64)
+    v_bound = torch.zeros(t_pad, n_mels, dtype=torch.float64)
+    v_ref[:T], v_bound[:T] = v, b
+    return l_ref, l_bound, v_ref, _slack(v_bound)
+
+
+def mel_signal(n, kind="mix", seed=1):
+    """fp32 test waves of n samples (shared by the CPU demonstrations and the GPU cases).
+    "mix": a 100 Hz -> 7 kHz chirp of amplitude 0.2 plus white noise of deviation 0.2 -- every band
+    of every frame has energy, so no band sits on spectral leakage alone.  The floor cases:
+    "zeros_after" (the mix, exact zeros from the middle on), "quiet_after" (the mix, from the
+    middle on at -60 dB), "loud_first" / "loud_last" (the mix at 1e-4, more than 8 in log10 power
+    below its first 160 samples / the span of its last frame, which stay at full level), "zeros", "noise1e-3" (white noise of deviation 1e-3: every log value is
+    negative).  (The seed is one at which no band of the one- and two-frame clips falls, by chance,
+    thousands of times below its neighbours: tests/test_parity_bounds.py asserts from the inputs
+    that at most 1 % of the bounds of any signal used are wider than 2^-6.)"""
+    g = torch.Generator().manual_seed(1000 * seed + n)
+    t = torch.arange(n, dtype=torch.float64) / 16000.0
+    dur = max(n / 16000.0, 1e-3)
+    chirp = 0.2 * torch.sin(2 * math.pi * (100.0 * t + 0.5 * (7000.0 - 100.0) / dur * t * t))
+    mix = (chirp + 0.2 * torch.randn(n, generator=g, dtype=torch.float64)).float()
+    h = n // 2
+    if kind == "mix":
+        return mix
+    if kind == "zeros_after":
+        mix[h:] = 0.0
+        return mix
+    if kind == "quiet_after":
+        mix[h:] *= 1e-3
+        return mix
+    if kind in ("loud_first", "loud_last"):
+        mix *= 1e-4
+        if kind == "loud_first":
+            mix[:MEL_HOP] *= 1e4
+        else:
+            mix[(n // MEL_HOP - 1) * MEL_HOP - MEL_HOP // 2:] *= 1e4
+        return mix
+    if kind == "zeros":
+        return torch.zeros(n)
+    if kind == "noise1e-3":
+        return (1e-3 * torch.randn(n, generator=g, dtype=torch.float64)).float()
+    raise ValueError(kind)
+
+
+MEL_N = (201, 319, 320, 1279, 1319, 1320, 4000, 4159, 40000)  # T = 1, 1, 2, 7, 8, 8, 25, 25, 250
+MEL_FLOOR_KINDS = ("zeros_after", "quiet_after", "loud_first", "loud_last", "zeros", "noise1e-3")
+MEL_FLOOR_N = 4159  # T = 25: three full blocks of 8 frames and one frame in the partial block
+
+
+# ---------------------------------------------------------------- time embedding (ls_elem.hip)
+LN_10000 = math.log(10000.0)
+
+
+def timestep_bound(t, dim, shift, flip=True):
+    """(ref, B), each (len(t), dim) fp64, for ls_timestep_embed / ls_timestep_embed_f32
+    (timestep_embed_kernel, timestep_embed_f32_kernel of ls_elem.hip); t the timesteps as the
+    kernel converts them to fp32 (integers, or the fp32 values themselves).
+
+        ref[:, i], ref[:, half + i] = cos, sin (flip) or sin, cos of t exp(-ln(10000) i / (half - shift))
+
+    in fp64, half = dim / 2.  The kernel's argument "t * expf(-9.210340371976184f * (float)i /
+    ((float)half - shift))" carries 7 roundings of at most 2^-23 each (any mode): the constant, the
+    product with i, the subtraction half - shift and the division -- four that reach expf's input x_i =
+    ln(10000) i / (half - shift) and so move its result by a relative |x_i| each --, expf itself
+    (2: 1 ulp of OCML's expf, rounded up), and the product with t.  The error of the argument is
+    therefore proportional to it, |d arg| <= (4 x_i + 3) 2^-23 |arg|, and sin and cos (slope <= 1)
+    move by no more; sinf / cosf add 4 2^-23 absolute (2 ulp of a result <= 1, rounded up).  At
+    i = 0 every step is exact (0 / d = 0, expf(0) = 1, t * 1 = t): only the 4 2^-23 remain.
+    The slack of gemm_bound on top."""
+    t = f64(t).reshape(-1, 1)
+    half = dim // 2
+    i = torch.arange(half, dtype=torch.float64)[None, :]
+    x = LN_10000 * i / (half - float(shift))
+    arg = t * torch.exp(-x)
+    rel = torch.where(i == 0, torch.zeros_like(x), (4 * x + 3) * E_F32)
+    b = _slack(rel * arg.abs() + 4 * E_F32)
+    sn, cs = torch.sin(arg), torch.cos(arg)
+    ref = torch.cat([cs, sn] if flip else [sn, cs], 1)
+    return ref, torch.cat([b, b], 1)
+
+
+def dot_bound(x, w, bias, silu_in):
+    """(ref, B), each (M, N) fp64, for ls_small_linear (small_linear_kernel, ls_elem.hip):
+    y = act(x) W^T + bias with x (M, K) fp32, W (N, K) bf16-rounded, bias (N,) fp32 or None, fp32 out.
+
+        B = 2^-24 |ref| + (2 K + 8 + 64 + 4) 2^-23 mag + [silu_in] sum_k |w_k| 8 2^-23 |x_k|
+        mag = sum_k |act(x_k) w_k| + |bias|
+
+    gemm_bound with k_terms = 2 K + 72: x is fp32 and W bf16, so -- unlike the MFMA GEMMs -- every
+    product "f[j] * xs[mm * K + k + j]" rounds: K products and K additions, plus the 8-wide inner
+    sum "s += ..." that is added to acc[mm] and the 64-lane wave_sum; gemm_bound's own + 4 holds the
+    bias.  (No single term passes through more than 1 + 8 + K / 512 + 6 + 1 of these roundings, so
+    the count is generous; it is the count an order-free restatement may use.)  With silu_in the
+    kernel evaluates silu(x_k) in fp32 before the sum: act_bound's evaluation term 8 2^-23 |x_k| on
+    every x_k, carried through |w_k|.  The result is stored unrounded (fp32): u_out = 2^-24."""
+    x, w = f64(x), f64(w)
+    K = x.shape[1]
+    a = _silu(x) if silu_in else x
+    ref, mag = _linear(a, w, bias)
+    b = gemm_bound(ref, mag, 2 * K + 8 + 64, torch.float32)
+    if silu_in:
+        b = b + _slack((8 * E_F32 * x.abs()) @ w.abs().T)
+    return ref, b
+
+
+TS_T = (1, 501, 951, 999)
+TS_DIMS = (320, 6)
+# (M, K, N): one row; the model's three layers' shapes; N % 4 = 1 (waves past N return early);
+# M = 9 / 19 (a last row chunk of 1 / 3 rows), K = 8 (one lane works) and K = 2048, M = 1024 (the limits)
+SMALL_LINEAR_CASES = ((1, 320, 1280), (2, 1280, 1280), (8, 1280, 3001), (9, 8, 5), (19, 2048, 7), (1024, 320, 6))

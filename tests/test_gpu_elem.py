@@ -5,7 +5,10 @@ around every output and inputs checked unchanged.  The whole-pipeline tests reac
 kernels at one pitch each and judge them by a Frobenius ratio.
 
 Also the argument checks: non-positive sizes and a channel offset outside the destination
-row return LS_ERR_INVALID with nothing launched."""
+row return LS_ERR_INVALID with nothing launched.
+
+The time embedding (ls_timestep_embed, ls_timestep_embed_f32, ls_small_linear -- temb of every
+ResNet block) follows at the end, with the bounds parity.timestep_bound / dot_bound."""
 import ctypes
 
 import pytest
@@ -242,3 +245,81 @@ def test_elem_argument_checks(gpu):
         P.assert_guard_intact(gg)
         assert bool((gg.view.contiguous().view(gg.bits_dtype) == (gg.sentinel if gg.bits_dtype != U8 else 0xA5)).all())
     assert int(step.item()) == 0
+
+
+# ---------------------------------------------------------------- the time embedding
+@pytest.mark.parametrize("shift", [0, 1])
+@pytest.mark.parametrize("flip", [True, False])
+@pytest.mark.parametrize("dim", P.TS_DIMS)
+def test_timestep_embed(gpu, dim, flip, shift):
+    """t = ts[*step] with step in 1 .. 4 (never the first entry), B = 1 and 2 identical rows,
+    dim 320 (the model's) and 6 (half = 3: most threads idle), both orders, shift 0 and 1."""
+    table = torch.tensor([7, *P.TS_T, 3], dtype=torch.int32)
+    td = dev(table)
+    worst = 0.0
+    for k, t in enumerate(P.TS_T, start=1):
+        assert int(table[k]) == t
+        for B in (1, 2):
+            step = torch.tensor([k], dtype=torch.int32, device=DEV)
+            g = P.guarded((B, dim), dtype=F32, device=DEV)
+            inputs = snaps(td, step)
+            ops.timestep_embed(td, step, B, dim, flip, float(shift), out=g.view)
+            ref, bound = P.timestep_bound(torch.full((B,), float(t)), dim, shift, flip)
+            worst = max(worst, check(f"timestep_embed t {t} B {B} dim {dim} flip {flip} shift {shift}", g, ref, bound, inputs))
+    print(f"timestep_embed dim {dim} flip {flip} shift {shift}: worst err/bound {worst:.3f}")
+
+
+@pytest.mark.parametrize("shift", [0, 1])
+@pytest.mark.parametrize("flip", [True, False])
+@pytest.mark.parametrize("dim", P.TS_DIMS)
+def test_timestep_embed_f32(gpu, dim, flip, shift):
+    """One block per sample: three distinct fractional timesteps, each row its own."""
+    t = torch.tensor([0.25, 500.5, 998.75], dtype=F32)
+    td = dev(t)
+    g = P.guarded((3, dim), dtype=F32, device=DEV)
+    inputs = snaps(td)
+    ops.timestep_embed_f32(td, dim, flip, float(shift), out=g.view)
+    ref, bound = P.timestep_bound(t, dim, shift, flip)
+    check(f"timestep_embed_f32 dim {dim} flip {flip} shift {shift}", g, ref, bound, inputs)
+
+
+@pytest.mark.parametrize("with_bias", [True, False])
+@pytest.mark.parametrize("silu_in", [False, True])
+@pytest.mark.parametrize("M,K,N", P.SMALL_LINEAR_CASES)
+def test_small_linear(gpu, M, K, N, silu_in, with_bias):
+    """fp32 x of deviation 2, bf16 W, fp32 out: the model's shapes (K 320 and 1280), N % 4 != 0
+    (the waves past N leave after the barrier), a last row chunk of 1 and 3 rows, K = 8 (one
+    working lane), and the limits K = 2048, M = 1024."""
+    x = 2.0 * rnd(M, K, seed=M + K)
+    w = P.bf16_round(rnd(N, K, seed=N + K + 1, scale=K ** -0.5))
+    b = rnd(N, seed=N + 2, scale=0.1) if with_bias else None
+    xd, wd, bd = dev(x), dev(w.to(BF)), None if b is None else dev(b)
+    g = P.guarded((M, N), dtype=F32, device=DEV)
+    inputs = snaps(xd, wd) + ([] if bd is None else snaps(bd))
+    ops.small_linear(xd, wd, bd, silu_in=silu_in, out=g.view)
+    ref, bound = P.dot_bound(x, w, b, silu_in)
+    check(f"small_linear {M}x{K}x{N} silu {silu_in} bias {with_bias}", g, ref, bound, inputs)
+
+
+def test_time_embedding_argument_checks(gpu):
+    """K % 8 != 0, K > 2048, M > 1024, an odd dim and B = 0: LS_ERR_INVALID, nothing launched
+    (the output keeps its sentinel)."""
+    from latentsync_amd import _lib
+    lib = _lib.load()
+    INVALID = 1
+    gf = P.guarded((64, 16), dtype=F32, device=DEV)
+    src = torch.zeros(4096, dtype=F32, device=DEV)
+    step = torch.zeros(1, dtype=torch.int32, device=DEV)
+    of, s, st = gf.view.data_ptr(), src.data_ptr(), step.data_ptr()
+    calls = []
+    for M, K in ((1, 12), (1, 4), (1, 2056), (1025, 8), (0, 8)):
+        calls.append((f"ls_small_linear M {M} K {K}", lib.ls_small_linear(s, M, K, s, s, 4, 0, of, None)))
+    for B, dim in ((1, 7), (2, 321), (0, 8), (-1, 8)):
+        calls.append((f"ls_timestep_embed B {B} dim {dim}", lib.ls_timestep_embed(s, st, B, dim, 1, 0.0, of, None)))
+        calls.append((f"ls_timestep_embed_f32 B {B} dim {dim}", lib.ls_timestep_embed_f32(s, B, dim, 1, 0.0, of, None)))
+    bad = [(n, rc) for n, rc in calls if rc != INVALID]
+    assert not bad, bad
+    assert lib.ls_last_error()
+    torch.cuda.synchronize()
+    P.assert_guard_intact(gf)
+    assert bool((gf.view.contiguous().view(gf.bits_dtype) == gf.sentinel).all())

@@ -8,6 +8,7 @@ whole-output Frobenius ratio (conftest.rel_err < 1e-2) lets the GEMM defects thr
 is kept on record here.  The fp8 attention (ls_attention_fp8) has its own restatement at the end: a
 walk of the keys in attn8_kernel's tile order, which must pass attn_fp8_bound on every case of the
 GPU file, and seven planted defects that must leave it."""
+import functools
 import math
 
 import pytest
@@ -1412,3 +1413,185 @@ def test_fp8_skipped_first_half_flush_rejected(name):
     res = fp8_defect_rows(name, [(r, dict(skip_flush=True)) for r in rows], "skipped first-half flush")
     assert sum(rej for _, _, rej, _, _ in res) >= len(res) // 2 > 0, res
     fp8_old_check_blind(name, res)
+
+
+# ---------------------------------------------------------------- Whisper log-mel (ls_log_mel)
+@functools.lru_cache(maxsize=None)
+def mel_fb(n_mels=80):
+    from latentsync_amd.audio import mel_filters
+    return torch.from_numpy(mel_filters(n_mels=n_mels))
+
+
+@functools.lru_cache(maxsize=None)
+def mel_oracle(n, kind, t_pad=None, n_mels=80):
+    return P.log_mel_bound(P.mel_signal(n, kind), mel_fb(n_mels), t_pad or n // P.MEL_HOP)
+
+
+def emulate_log_mel(wave, filters, t_pad, hann="periodic", pad="reflect", block_floor=False, frame_offset=0,
+                    truncate=False):
+    """log_mel_kernel + mel_norm_kernel restated in fp32 torch: the window and the twiddles as fp32
+    tables, fp32 products and sums (torch's fp32 matmul: another order than the kernel's chain,
+    which the bound allows), log10, the clip-wide floor, (x + 4) / 4, bf16 round-to-nearest.
+    Returns (l fp32 (T, n_mels), v (t_pad, n_mels) as fp32).  The switches plant one defect each."""
+    x = wave.float()
+    n = x.numel()
+    T = n // P.MEL_HOP
+    m = torch.arange(P.MEL_NFFT)
+    win = 0.5 - 0.5 * torch.cos(2.0 * math.pi * m.double() / (P.MEL_NFFT if hann == "periodic" else P.MEL_NFFT - 1)).float()
+    j = (torch.arange(T)[:, None] + frame_offset) * P.MEL_HOP + m[None, :] - P.MEL_NFFT // 2
+    if pad == "reflect":
+        j = j.abs()
+        j = torch.where(j >= n, 2 * (n - 1) - j, j).clamp(0, n - 1)
+        xw = x[j] * win
+    else:
+        inside = (j >= 0) & (j < n)
+        xw = torch.where(inside, x[j.clamp(0, n - 1)], torch.zeros(())) * win
+    ph = 2.0 * math.pi * ((torch.arange(P.MEL_NFREQ)[:, None] * m[None, :]) % P.MEL_NFFT).double() / P.MEL_NFFT
+    re, im = xw @ torch.cos(ph).float().T, -(xw @ torch.sin(ph).float().T)
+    s = (re * re + im * im) @ filters.float().T
+    l = torch.log10(s.clamp_min(1e-10))
+    if block_floor:
+        nb = -(-T // P.MEL_BLOCK)
+        lp = torch.full((nb * P.MEL_BLOCK, l.shape[1]), -float("inf"))
+        lp[:T] = l
+        fl = (lp.reshape(nb, -1).amax(1) - 8.0).repeat_interleave(P.MEL_BLOCK)[:T, None]
+    else:
+        fl = l.max() - 8.0
+    v32 = (torch.maximum(l, fl) + 4.0) / 4.0
+    vb = (v32.view(torch.int32) & -65536).view(torch.float32) if truncate else v32.to(torch.bfloat16).float()
+    v = torch.zeros(t_pad, l.shape[1])
+    v[:T] = vb
+    return l, v
+
+
+# every (n, signal, n_mels) of tests/test_gpu_edges_audio.py
+MEL_SIGNALS = [(n, "mix", 80) for n in P.MEL_N] + [(P.MEL_FLOOR_N, k, 80) for k in P.MEL_FLOOR_KINDS] + [(4159, "mix", 128)]
+
+
+@pytest.mark.parametrize("n,kind,n_mels", MEL_SIGNALS)
+def test_log_mel_emulation_passes_and_bound_is_narrow(n, kind, n_mels):
+    """The fp32 restatement passes both bounds on every signal the GPU file uses, and the bound
+    cannot hide a failure behind its width: at most 1 % of the fp32 log-mel elements of a signal
+    have a half-width above 2^-6 (those are still checked, against their own bound)."""
+    T = n // P.MEL_HOP
+    l_ref, l_b, v_ref, v_b = mel_oracle(n, kind, T + 3, n_mels)
+    l, v = emulate_log_mel(P.mel_signal(n, kind), mel_fb(n_mels), T + 3)
+    wl = P.assert_elementwise(l, l_ref, l_b, name="log-mel")
+    wv = P.assert_elementwise(v, v_ref, v_b, name="normalised mel")
+    assert float(v[T:].abs().max()) == 0.0
+    wide = float((l_b > 2.0 ** -6).double().mean())
+    print(f"log-mel emulation n {n} {kind} mels {n_mels}: err/bound l {wl:.3f} v {wv:.3f}; half-width median {float(l_b.median()):.2e} "
+          f"max {float(l_b.max()):.2e}, {100 * wide:.2f} % above 2^-6")
+    assert wide <= 0.01
+    if kind == "zeros":
+        assert bool((v[:T] == -1.5).all())
+    if kind == "noise1e-3":
+        assert float(l_ref.max()) < 0  # the negative branch of the ordered-uint maximum
+
+
+def mel_mutant_ratios(n, kind, **defect):
+    l_ref, l_b, v_ref, v_b = mel_oracle(n, kind)
+    l, v = emulate_log_mel(P.mel_signal(n, kind), mel_fb(), n // P.MEL_HOP, **defect)
+    return (P.f64(l) - l_ref).abs() / l_b, (P.f64(v) - v_ref).abs() / v_b
+
+
+def test_log_mel_symmetric_hann_rejected():
+    rl, rv = mel_mutant_ratios(4159, "mix", hann="symmetric")
+    print(f"symmetric Hann: {100 * float((rl > 1).double().mean()):.1f} % of the fp32 log-mel values outside (worst "
+          f"{float(rl.max()):.1f}), {100 * float((rv > 1).double().mean()):.1f} % of the bf16 outputs (worst {float(rv.max()):.1f})")
+    assert float(rl.max()) > 4 and float((rl > 1).double().mean()) > 0.3
+    assert float(rv.max()) > 1
+
+
+def test_log_mel_zero_padding_rejected():
+    """Zero instead of reflect padding: only the frames whose window leaves the clip differ."""
+    rl, rv = mel_mutant_ratios(4159, "mix", pad="zero")
+    bad = sorted(set(torch.nonzero(rl > 1)[:, 0].tolist()))
+    print(f"zero padding: worst err/bound l {float(rl.max()):.0f} v {float(rv.max()):.0f}, frames {bad}")
+    assert float(rl.max()) > 10 and float(rv.max()) > 1
+    assert set(bad) <= {0, 1, 24} and 0 in bad
+
+
+def test_log_mel_block_floor_rejected():
+    """The floor from each block's own maximum: invisible in l, caught in v wherever a quiet
+    block sits more than 8 below the clip's loudest frame."""
+    rl, rv = mel_mutant_ratios(P.MEL_FLOOR_N, "zeros_after", block_floor=True)
+    assert float(rl.max()) <= 1
+    print(f"per-block floor: worst err/bound v {float(rv.max()):.0f}")
+    assert float(rv.max()) > 50
+    for kind in ("loud_first", "loud_last"):  # these two cases separate the floors as well
+        assert float(mel_mutant_ratios(P.MEL_FLOOR_N, kind, block_floor=True)[1].max()) > 1, kind
+
+
+def test_log_mel_frame_offset_rejected():
+    rl, rv = mel_mutant_ratios(4159, "mix", frame_offset=1)
+    print(f"one frame of offset: worst err/bound l {float(rl.max()):.0f} v {float(rv.max()):.0f}")
+    assert float(rl.max()) > 10 and float(rv.max()) > 10
+
+
+def test_log_mel_truncation_rejected():
+    rl, rv = mel_mutant_ratios(4159, "mix", truncate=True)
+    assert float(rl.max()) <= 1
+    print(f"bf16 truncation: worst err/bound v {float(rv.max()):.2f}, {100 * float((rv > 1).double().mean()):.1f} % outside")
+    assert 1.3 < float(rv.max()) < 2.1  # up to a full ulp instead of half of one
+
+
+# ---------------------------------------------------------------- time embedding (ls_elem.hip)
+def emulate_timestep(t, dim, shift, flip, swap=False, no_shift=False):
+    """timestep_embed_kernel in fp32 torch, operation by operation."""
+    half = dim // 2
+    i = torch.arange(half, dtype=torch.float32)
+    den = torch.tensor(float(half), dtype=torch.float32) - (0.0 if no_shift else torch.tensor(float(shift), dtype=torch.float32))
+    e = torch.exp(torch.tensor(-9.210340371976184, dtype=torch.float32) * i / den)
+    arg = torch.as_tensor(t, dtype=torch.float32).reshape(-1, 1) * e[None, :]
+    sn, cs = torch.sin(arg), torch.cos(arg)
+    return torch.cat([cs, sn] if bool(flip) != swap else [sn, cs], 1)
+
+
+TS_VALUES = [float(t) for t in P.TS_T] + [0.25, 500.5, 998.75]
+
+
+@pytest.mark.parametrize("dim", P.TS_DIMS)
+@pytest.mark.parametrize("flip", [True, False])
+@pytest.mark.parametrize("shift", [0, 1])
+def test_timestep_emulation_passes_and_mutants_rejected(dim, flip, shift):
+    ref, b = P.timestep_bound(torch.tensor(TS_VALUES), dim, shift, flip)
+    worst = P.assert_elementwise(emulate_timestep(TS_VALUES, dim, shift, flip), ref, b, name="timestep")
+    print(f"timestep emulation dim {dim} flip {flip} shift {shift}: err/bound {worst:.3f}, widest bound {float(b.max()):.2e}")
+    assert float(b.max()) < 2e-3  # no wider than the absolute tolerance it replaces
+    with pytest.raises(AssertionError, match="err/bound"):  # sin and cos swapped under flip
+        P.assert_elementwise(emulate_timestep(TS_VALUES, dim, shift, flip, swap=True), ref, b)
+    if shift:  # half where half - shift belongs
+        with pytest.raises(AssertionError, match="err/bound"):
+            P.assert_elementwise(emulate_timestep(TS_VALUES, dim, shift, flip, no_shift=True), ref, b)
+
+
+def small_linear_case(M, K, N, seed=0):
+    """fp32 x (M, K) of deviation 2 (SiLU is far from the identity), bf16-rounded W (N, K), fp32 bias."""
+    x = 2.0 * rnd(M, K, seed=seed + M + K)
+    w = P.bf16_round(rnd(N, K, seed=seed + N + K + 1, scale=1 / math.sqrt(K)))
+    return x, w, rnd(N, seed=seed + N + 2, scale=0.1)
+
+
+def emulate_small_linear(x, w, bias, silu_in):
+    a = x * torch.sigmoid(x) if silu_in else x
+    y = a @ w.T
+    return y if bias is None else y + bias
+
+
+@pytest.mark.parametrize("M,K,N", P.SMALL_LINEAR_CASES)
+@pytest.mark.parametrize("silu_in", [False, True])
+def test_small_linear_emulation_passes_and_mutants_rejected(M, K, N, silu_in):
+    x, w, b = small_linear_case(M, K, N)
+    for bias in (b, None):
+        ref, bound = P.dot_bound(x, w, bias, silu_in)
+        worst = P.assert_elementwise(emulate_small_linear(x, w, bias, silu_in), ref, bound, name="small_linear")
+        with pytest.raises(AssertionError, match="err/bound"):  # SiLU skipped / applied unasked
+            P.assert_elementwise(emulate_small_linear(x, w, bias, not silu_in), ref, bound)
+    ref, bound = P.dot_bound(x, w, b, silu_in)
+    col = int(b.abs().argmax())
+    b2 = b.clone()
+    b2[col] = 0.0
+    with pytest.raises(AssertionError, match=rf"col {col};"):  # a dropped bias column
+        P.assert_elementwise(emulate_small_linear(x, w, b2, silu_in), ref, bound)
+    print(f"small_linear emulation {M}x{K}x{N} silu {silu_in}: err/bound {worst:.3f}")
